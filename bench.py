@@ -1,6 +1,7 @@
 """Benchmark: depth maps/sec of the TransMVSNet hot path at DTU 864x1152, N=5, 48/32/8.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode replica|views] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode replica|views] [--dump-outputs DIR]
+    python bench.py --full [...] [--no-cpu-baseline] [--profile-steps P] [--e2e-steps E] [--train-steps T]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +18,19 @@ is outside the timed step. Multi-GPU:
                        (sum w*sim, sum w) per stage (transmvsnet_amd.distributed); with more
                        ranks than source views, replicas x view-shard groups (8 ranks: 2 x 4).
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the
+--dump-outputs files, the result line. --full adds every secondary measurement to that line: the
+eager-launch timing, per-kernel HIP-event durations and rooflines, the coherent-hypotheses cost
+volume, end_to_end, batch2_concurrent, train_depth_stages, cpu_baseline and abs_depth_l1_vs_ref
+(their knobs -- --no-cpu-baseline, --profile-steps, --e2e-steps, ... -- act only under --full).
+
+--dump-outputs DIR writes what the last timed step returned (forward_features' dict) as
+DIR/<name>.npy, float32: depth / photo_confidence / prob_volume / depth_values (the caller's
+top-level entries, = stage 3) and stage1_* / stage2_*; DIR/manifest.json lists each array's full
+shape. An array above DUMP_MAX_ELEMS elements is stored as a fixed sample of its flattened
+elements (indices from numpy's default_rng(DUMP_SEED), sorted), so every file set stays below 64 MB.
+Inputs and weights are seeded: the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -38,6 +52,8 @@ PEAK_F32_MFMA_TFS = 157.3  # MI355X_MICROARCH.md: fp32 MFMA dense peak
 # vector-memory address unit (TA) gather rate: 64 B/clk/CU (a 64-lane 16-B load costs >= 16 cycles,
 # measured by scripts/micro/ta_mask.hip) x 256 CUs x 2.4 GHz
 PEAK_TA_GBS = 64 * 256 * 2.4
+DUMP_MAX_ELEMS = 1 << 20   # --dump-outputs: larger arrays are sampled down to this many elements
+DUMP_SEED = 0
 
 
 def _args():
@@ -46,6 +62,11 @@ def _args():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--mode", choices=("replica", "views"), default="replica")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (eager timing, per-kernel events and rooflines, "
+                         "end_to_end, batch2, training step, cpu_baseline + parity); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; large arrays sampled)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
                     help="nccl = RCCL (the product path); gloo only to rehearse the launcher with more ranks than GPUs")
@@ -115,6 +136,27 @@ def make_inputs(device, seed_feat=2):
     proj = synthetic.synthetic_cameras(NVIEWS, H, W, seed=1)
     dv = synthetic.synthetic_depth_values(1)
     return synthetic.stacked_features(NVIEWS, H, W, seed=seed_feat), proj, dv
+
+
+def dump_outputs(out, directory):
+    """The last timed step's outputs -> directory/<name>.npy (float32) + manifest.json (module docstring)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}   # the caller's top-level entries (= stage 3)
+    for stage in ("stage1", "stage2"):
+        arrays.update({f"{stage}_{k}": v for k, v in out[stage].items()})
+    manifest = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        sampled = flat.numel() > DUMP_MAX_ELEMS
+        if sampled:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), DUMP_MAX_ELEMS, replace=False))
+            a = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        else:
+            a = t.detach().cpu().numpy()
+        np.save(os.path.join(directory, f"{name}.npy"), a.astype(np.float32, copy=False))
+        manifest[name] = {"shape": list(t.shape), "sampled": sampled, "stored_elems": int(a.size)}
+    with open(os.path.join(directory, "manifest.json"), "w") as f:
+        json.dump({"arrays": manifest, "sample_seed": DUMP_SEED, "max_elems": DUMP_MAX_ELEMS}, f, indent=1)
 
 
 def batch2_timing(model, feats, proj, dv_dev, steps, graphed):
@@ -305,6 +347,37 @@ def run(args, world, rank, local):
                 raise RuntimeError(f"ranks disagree (steps, depth checksum): {allc}")
             ranks_ok = {"ranks": world, "steps_each": args.steps, "depth_checksum": allc[0][1]}
 
+        maps_per_step = shard.replicas if shard is not None else (1 if args.mode == "views" else world)
+        headline = {
+            "metric": "depth maps/sec @ DTU 864x1152 N=5 (48/32/8 hyp); Abs depth L1 vs ref",
+            "value": round(maps_per_step * args.steps / elapsed, 3),
+            "unit": "depth_maps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak" if args.mode == "replica" else "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic (seeded FeatureNet-shaped features, DTU-like cameras, key-seeded random weights)",
+            "config": {"workload": "DTU 864x1152, N=5 views, cascade 48/32/8, B=1, hot path from FeatureNet "
+                                   "outputs (FMT+pathway+stage glue+cost volume+CostRegNet+softmax/WTA)",
+                       "global_batch": maps_per_step, "parallelism": f"{args.mode}{world}",
+                       "launch": "hip_graph replay" if graphed else "eager"},
+            "full": args.full,
+        }
+        if ranks_ok is not None:
+            headline["ranks_check"] = ranks_ok
+        if args.dump_outputs and rank == 0:
+            dump_outputs(out, args.dump_outputs)
+        if not args.full:  # a plain run: the headline only
+            if rank == 0:
+                print(json.dumps(headline), flush=True)
+            if world > 1:
+                dist.destroy_process_group()
+            return
+
         eager = None
         if graphed:
             # the same K steps launched eagerly from Python, outside the timed region: the form a caller
@@ -355,8 +428,6 @@ def run(args, world, rank, local):
     train = (train_timing(args.train_steps, dev, world, use_graph=not args.no_graph)
              if args.train_steps > 0 and shard is None else None)
 
-    maps_per_step = shard.replicas if shard is not None else (1 if args.mode == "views" else world)
-    value = maps_per_step * args.steps / elapsed
     per_kernel = {}
     for n, ms in spans:
         per_kernel.setdefault(n, []).append(ms)
@@ -436,22 +507,7 @@ def run(args, world, rank, local):
 
     if rank == 0:
         line = {
-            "metric": "depth maps/sec @ DTU 864x1152 N=5 (48/32/8 hyp); Abs depth L1 vs ref",
-            "value": round(value, 3),
-            "unit": "depth_maps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak" if args.mode == "replica" else "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (seeded FeatureNet-shaped features, DTU-like cameras, key-seeded random weights)",
-            "config": {"workload": "DTU 864x1152, N=5 views, cascade 48/32/8, B=1, hot path from FeatureNet "
-                                   "outputs (FMT+pathway+stage glue+cost volume+CostRegNet+softmax/WTA)",
-                       "global_batch": maps_per_step, "parallelism": f"{args.mode}{world}",
-                       "launch": "hip_graph replay" if graphed else "eager"},
+            **headline,
             "eager": eager,
             "roofline": dominant,
             "roofline_kernels": kern,
@@ -466,8 +522,6 @@ def run(args, world, rank, local):
             "batch2_concurrent": batch2,
             "train_depth_stages": train,
         }
-        if ranks_ok is not None:
-            line["ranks_check"] = ranks_ok
         if comm is not None:
             line["allreduce"] = comm
         print(json.dumps(line), flush=True)

@@ -9,7 +9,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for v in default "$@"; do
   if [ "$v" = default ]; then unset TMVS_LIB_PATH; else export TMVS_LIB_PATH=variants/$v/libtransmvs_hip.so; fi
-  timeout -k 10 200 rocprofv3 --kernel-trace -d $OUT/$v -o run -- python3 bench.py --steps 10 --warmup 3 \
+  timeout -k 10 200 rocprofv3 --kernel-trace -d $OUT/$v -o run -- python3 bench.py --full --steps 10 --warmup 3 \
       --no-cpu-baseline --e2e-steps 0 --train-steps 0 > $OUT/$v.log 2>&1 || exit $?
   echo "== $v $(grep "\"metric\"" $OUT/$v.log | tail -1 | cut -c1-160)"
   python3 scripts/diag/kernel_grid_times.py $OUT/$v/run_results.db $PATS

@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for v in "$@"; do
   if [ "$v" = default ]; then unset TMVS_LIB_PATH; else export TMVS_LIB_PATH=variants/$v/libtransmvs_hip.so; fi
-  timeout -k 10 240 rocprofv3 --kernel-trace -d $OUT/$v -o run --output-format csv -- python3 bench.py --steps 10 \
+  timeout -k 10 240 rocprofv3 --kernel-trace -d $OUT/$v -o run --output-format csv -- python3 bench.py --full --steps 10 \
       --warmup 3 --no-cpu-baseline --e2e-steps 0 --train-steps 0 --batch2-steps 0 > $OUT/$v.log 2>&1
   rc=$?
   if [ $rc -ne 0 ]; then echo "== $v rc=$rc"; tail -3 $OUT/$v.log; exit $rc; fi

@@ -14,7 +14,7 @@ TMVS_LIB_PATH=variants/c5chunk/libtransmvs_hip.so TMVS_REPORT_DIR=$O/fullsize_c5
   > $O/pytest_c5chunk.log 2>&1; rc2=$?
 tail -5 $O/pytest_c5chunk.log
 [ $rc2 -eq 0 ] || [ $rc2 -eq 1 ] || exit $rc2
-timeout -k 10 300 python bench.py > $O/bench.log 2>&1 || exit $?
+timeout -k 10 300 python bench.py --full > $O/bench.log 2>&1 || exit $?
 tail -c 3000 $O/bench.log
 timeout -k 10 300 python -u -m pytest tests/test_gpu_batch.py -v --timeout 250 --timeout-method thread \
   > $O/pytest_batch.log 2>&1; echo "batch rc=$?"

@@ -7,6 +7,6 @@ TMVS_REPORT_DIR=$O/fullsize timeout -k 10 1000 python -u -m pytest tests -m gpu 
   > $O/pytest_gpu.log 2>&1; rc=$?
 tail -12 $O/pytest_gpu.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
-timeout -k 10 300 python bench.py > $O/bench.log 2>&1 || exit $?
+timeout -k 10 300 python bench.py --full > $O/bench.log 2>&1 || exit $?
 tail -c 1500 $O/bench.log
 exit $rc

@@ -13,10 +13,10 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -v -s --timeout 300 --timeou
 rc=$?
 tail -3 $OUT/pytest_gpu.log
 [ $rc -le 1 ] || exit $rc
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || exit $?
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || exit $?
 tail -1 $OUT/bench.json | cut -c1-400
-timeout -k 10 300 python bench.py --gpus 2 --dist-backend gloo --mode views --steps 5 --warmup 2 --e2e-steps 0 \
+timeout -k 10 300 python bench.py --full --gpus 2 --dist-backend gloo --mode views --steps 5 --warmup 2 --e2e-steps 0 \
     > $OUT/bench_views2_gloo.json 2> $OUT/bench_views2_gloo.err || exit $?
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d $OUT/trace -o run --output-format csv -- \
-    python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --e2e-steps 0 --train-steps 0 > $OUT/trace.log 2>&1 || exit $?
+    python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --e2e-steps 0 --train-steps 0 > $OUT/trace.log 2>&1 || exit $?
 exit $rc

@@ -7,5 +7,5 @@ export TMPDIR=/tmp
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d $OUT/trace -o run --output-format csv -- \
-    python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --profile-steps 0 > $OUT/trace.log 2>&1 || exit $?
+    python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --profile-steps 0 > $OUT/trace.log 2>&1 || exit $?
 python3 scripts/trace_table.py $OUT/trace/run_kernel_trace.csv | tee $OUT/trace_table.txt

@@ -10,7 +10,7 @@ echo "list rc=$?"
 run_pass() {
   local name=$1; shift
   timeout -k 10 300 rocprofv3 --pmc "$@" -T -d $OUT/pmc_$name -o run --output-format csv -- \
-      python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 0 > $OUT/pmc_$name.log 2>&1
+      python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 0 > $OUT/pmc_$name.log 2>&1
   local rc=$?
   echo "pass $name rc=$rc"
   return $rc

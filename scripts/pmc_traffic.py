@@ -4,7 +4,7 @@
 
 Correction (MI355X_MICROARCH.md, HBM section): on gfx950 FETCH_SIZE reports half the bytes of a
 16 B/lane read, so bytes_read = 2 x FETCH_SIZE; WRITE_SIZE is exact for 16 B/lane stores. Both
-counters are in KiB. The passes run bench.py with --steps 2 --warmup 1 --profile-steps 0 (3
+counters are in KiB. The passes run bench.py --full with --steps 2 --warmup 1 --profile-steps 0 (3
 forward steps, counted by fmt_embed_kernel dispatches); traffic per depth map = sum over one
 step's dispatches of the kernels behind one C-ABI entry point (the same grouping as bench.py's
 HIP-event `achieved`).
