@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TMVS_ABI_VERSION 9
+#define TMVS_ABI_VERSION 10
 
 #define TMVS_OK 0
 #define TMVS_ERR_ARG (-1)    /* null pointer / non-positive size / bad enum        */
@@ -481,6 +481,39 @@ int tmvs_conv2d_bn_relu(const float* x, int batch, int cin, int height, int widt
  *             they are (the reference reuses one buffer across cameras).                         */
 int tmvs_fusibile(const float* rgbd, const float* cams, int n_views, int height, int width, int ref_view,
                   int consistent_threshold, float depth_threshold, float* coord, float* texture, void* stream);
+
+/* Dynamic geometric-consistency filter of the Tanks & Temples output path (dynamic_fusion.py:78-280,
+ * scripts/test_tnt.sh) for one reference view, one launch: per pixel the reproject / reproject-back check
+ * against every source view at the nine nested tolerance levels i = 2..10 (pixel distance < i/4, relative
+ * depth difference < i/1300), the dynamic rule geo = (#level-10 >= thres_view) OR any_{i=2..n_src}
+ * (#level-i >= i), the photometric mask, the averaged depth and its world point. Float32 matrices,
+ * float64 per-pixel arithmetic, float32 casts where the reference's numpy dtypes cast.
+ *   depths      : [n_views][H][W] depth maps of every view of the scan
+ *   src_views   : [n_src] int32 (DEVICE) view indices into depths, in the pair file's order. The host
+ *                 side cannot read them: the CALLER guarantees each is in [0, n_views) and differs
+ *                 from ref_view (transmvsnet_amd.dynamic_fusion.filter_view validates them).
+ *   pair_blocks : [n_src][TMVS_DYNFUSE_PAIR_FLOATS], per (reference, source) pair the float32 matrices
+ *                 row-major: inv(K_ref) [0,9), rows 0-2 of E_src inv(E_ref) [9,21), K_src [21,30),
+ *                 inv(K_src) [30,39), rows 0-2 of E_ref inv(E_src) [39,51), K_ref [51,60), pad
+ *   ref_block   : [TMVS_DYNFUSE_REF_FLOATS]: inv(K_ref) [0,9), rows 0-2 of inv(E_ref) [9,21), pad
+ *   confidence  : [H][W] of the reference view; photo = confidence > photo_threshold
+ *   thres_view >= 1; 1 <= n_src <= TMVS_DYNFUSE_MAX_SRC (the reference has nine levels)
+ *   subpixel_bits: 5 = cv2.remap's INTER_LINEAR fixed-point path (coordinates rounded to 1/32 pixel),
+ *                 0 = exact fractional weights; anything else is TMVS_ERR_ARG
+ *   geo_count   : [H][W] uint8, sources passing the loosest level
+ *   mask        : [H][W] uint8, TMVS_DYNFUSE_PHOTO | TMVS_DYNFUSE_GEO | TMVS_DYNFUSE_FINAL
+ *   depth_avg   : [H][W] (sum of the level-10 reprojected depths + own depth) / (geo_count + 1)
+ *   xyz         : [H][W][3] world point of depth_avg where FINAL, 0 elsewhere                      */
+#define TMVS_DYNFUSE_PAIR_FLOATS 64
+#define TMVS_DYNFUSE_REF_FLOATS 24
+#define TMVS_DYNFUSE_MAX_SRC 10
+#define TMVS_DYNFUSE_PHOTO 1
+#define TMVS_DYNFUSE_GEO 2
+#define TMVS_DYNFUSE_FINAL 4
+int tmvs_dynamic_fusion(const float* depths, int n_views, int height, int width, int ref_view, const int* src_views,
+                        int n_src, const float* pair_blocks, const float* ref_block, const float* confidence,
+                        float photo_threshold, int thres_view, int subpixel_bits, unsigned char* geo_count,
+                        unsigned char* mask, float* depth_avg, float* xyz, void* stream);
 
 /* ------------------------------------------------------------------ training losses
  * entropy_loss (models/module.py:495-531) of one stage, as trans_mvsnet_loss / focal_loss_bld

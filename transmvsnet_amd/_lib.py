@@ -56,6 +56,7 @@ SIGNATURES = {
     "tmvs_conv2d_pack": (I, [P, I, I, I, P]),
     "tmvs_conv2d_bn_relu": (I, [P, I, I, I, I, P, I, I, I, P, P, I, P, P]),
     "tmvs_fusibile": (I, [P, P, I, I, I, I, I, F, P, P, P]),
+    "tmvs_dynamic_fusion": (I, [P, I, I, I, I, P, I, P, P, P, F, I, I, P, P, P, P, P]),
     "tmvs_entropy_loss_workspace": (S, [I, I, I]),
     "tmvs_entropy_loss": (I, [P, P, I, P, P, I, I, I, I, F, P, S, P, P, P, P, P]),
     "tmvs_depth_metrics_workspace": (S, [I]),
@@ -107,7 +108,7 @@ SIGNATURES = {
     "tmvs_softmax_backward": (I, [P, P, I, I, I, I, P, P]),
 }
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 PW_NPARAMS = 201
 ENC_NPARAMS = 8544
 KV_NFLOATS = 160
@@ -116,6 +117,10 @@ WARP_ROT_PLAIN = 2
 WARP_BWD_PLANES = 4
 CONV_TRANSPOSED = 1
 CONV_ACCUMULATE = 2
+DYNFUSE_PAIR_FLOATS = 64
+DYNFUSE_REF_FLOATS = 24
+DYNFUSE_MAX_SRC = 10
+DYNFUSE_PHOTO, DYNFUSE_GEO, DYNFUSE_FINAL = 1, 2, 4
 
 
 class CostRegWeights(ctypes.Structure):
