@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TMVS_ABI_VERSION 10
+#define TMVS_ABI_VERSION 11
 
 #define TMVS_OK 0
 #define TMVS_ERR_ARG (-1)    /* null pointer / non-positive size / bad enum        */
@@ -514,6 +514,48 @@ int tmvs_dynamic_fusion(const float* depths, int n_views, int height, int width,
                         int n_src, const float* pair_blocks, const float* ref_block, const float* confidence,
                         float photo_threshold, int thres_view, int subpixel_bits, unsigned char* geo_count,
                         unsigned char* mask, float* depth_avg, float* xyz, void* stream);
+
+/* The stage between the network and either fusion kernel, for one reference view, one launch: the body of
+ * test.py:119-158 (cv2.resize of the two coarse confidence maps, their product with the fine one, the mask
+ * on the depth map, utils.depth_normal utils.py:11-22, the 8-bit colours) and fusibile's decode of the PNG
+ * test.py writes (main.cpp:126-138). Each step runs in the dtype numpy / OpenCV use, so every output is
+ * bitwise what transmvsnet_amd.data.resize_bilinear, fusion.depth_normal and fusion.rgbd_from_images give.
+ *   depth, conf3 : [H][W]      the stage-3 depth and photometric confidence (outputs["depth"], ["photo_confidence"])
+ *   conf2, conf1 : [H/2][W/2], [H/4][W/4] the stage-2 and stage-1 confidences; H and W positive multiples of 4
+ *   image        : [3][H][W] RGB in [0, 1] (the reference view as the network read it), or NULL
+ *   conf_threshold: 0.01 in the reference (compared as float32); depth_min < depth_max: 425, 935
+ *   conf_final   : [H][W] (conf3 * resize(conf1)) * resize(conf2)
+ *   depth_masked : [H][W] 0 where conf_final < conf_threshold (a NaN confidence does not mask), else depth
+ *   rgba_u8      : [H][W][4] uint8 (R, G, B, alpha), the channels of the PNG cv2.imwrite stores for the
+ *                  reference's BGRA array: uint8(clip(image * 255, 0, 255)) and alpha =
+ *                  uint8((clip(depth_masked, depth_min, depth_max) - depth_min) / (depth_max - depth_min) * 255);
+ *                  4-byte aligned, or NULL
+ *   rgbd         : [H][W][4] float (B, G, R, depth) as tmvs_fusibile reads it: the 8-bit values * (1 / 255.)
+ *                  and depth = 425 + 512 * alpha / 255 (the reference's 510-vs-512 mismatch is kept);
+ *                  16-byte aligned (slot v of a [V][H][W][4] slab is), or NULL
+ * rgba_u8 or rgbd without an image is TMVS_ERR_ARG; H or W not a multiple of 4 is TMVS_ERR_SHAPE.     */
+int tmvs_depth_postprocess(const float* depth, const float* conf3, const float* conf2, const float* conf1,
+                           const float* image, int height, int width, float conf_threshold, float depth_min,
+                           float depth_max, float* conf_final, float* depth_masked, unsigned char* rgba_u8,
+                           float* rgbd, void* stream);
+
+/* ------------------------------------------------------------------ input side
+ * general_eval.read_img (:99-103) + the cv2.resize(INTER_LINEAR) of scale_mvs_input (general_eval.py:106-124)
+ * as transmvsnet_amd.data.resize_bilinear restates it + the HWC -> CHW transpose, for one image: each tap is
+ * float32(uint8) / 255.0f, then the float32 lerp a * (1 - t) + b * t along x and then along y.
+ *   src_u8      : [src_h][src_w][3] uint8, the decoded image
+ *   x0, x1, tx  : [dst_w] int32, int32, float: left / right source column and fraction per output column
+ *   y0, y1, ty  : [dst_h] likewise per output row (all DEVICE; transmvsnet_amd.data.resize_axis builds
+ *                 them; indices outside the source are clamped into it)
+ *   dst         : [3][dst_h][dst_w]
+ * tmvs_resize_bilinear_f32 is the same resize of an already loaded image, src [channels][src_h][src_w]
+ * float -> dst [channels][dst_h][dst_w] (the readers' second resize to the first view's size).          */
+int tmvs_resize_bilinear_u8(const unsigned char* src_u8, int src_h, int src_w, const int* x0, const int* x1,
+                            const float* tx, const int* y0, const int* y1, const float* ty, int dst_h, int dst_w,
+                            float* dst, void* stream);
+int tmvs_resize_bilinear_f32(const float* src, int channels, int src_h, int src_w, const int* x0, const int* x1,
+                             const float* tx, const int* y0, const int* y1, const float* ty, int dst_h, int dst_w,
+                             float* dst, void* stream);
 
 /* ------------------------------------------------------------------ training losses
  * entropy_loss (models/module.py:495-531) of one stage, as trans_mvsnet_loss / focal_loss_bld

@@ -57,6 +57,9 @@ SIGNATURES = {
     "tmvs_conv2d_bn_relu": (I, [P, I, I, I, I, P, I, I, I, P, P, I, P, P]),
     "tmvs_fusibile": (I, [P, P, I, I, I, I, I, F, P, P, P]),
     "tmvs_dynamic_fusion": (I, [P, I, I, I, I, P, I, P, P, P, F, I, I, P, P, P, P, P]),
+    "tmvs_depth_postprocess": (I, [P, P, P, P, P, I, I, F, F, F, P, P, P, P, P]),
+    "tmvs_resize_bilinear_u8": (I, [P, I, I, P, P, P, P, P, P, I, I, P, P]),
+    "tmvs_resize_bilinear_f32": (I, [P, I, I, I, P, P, P, P, P, P, I, I, P, P]),
     "tmvs_entropy_loss_workspace": (S, [I, I, I]),
     "tmvs_entropy_loss": (I, [P, P, I, P, P, I, I, I, I, F, P, S, P, P, P, P, P]),
     "tmvs_depth_metrics_workspace": (S, [I]),
@@ -108,7 +111,7 @@ SIGNATURES = {
     "tmvs_softmax_backward": (I, [P, P, I, I, I, I, P, P]),
 }
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 PW_NPARAMS = 201
 ENC_NPARAMS = 8544
 KV_NFLOATS = 160

@@ -113,34 +113,35 @@ def read_img(filename):
     return np.array(Image.open(filename), dtype=np.float32) / 255.0
 
 
+def resize_axis(n_out, n_in):
+    """One axis of resize_bilinear: per output index the left and right source index (clamped to the
+    image) and the float32 fraction of the source coordinate (i + 0.5) * (n_in / n_out) - 0.5, forced
+    to 0 where the left neighbour is clamped at either border."""
+    f = (np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5
+    i0 = np.floor(f)
+    t = (f - i0).astype(np.float32)
+    i0 = i0.astype(np.int64)
+    t = np.where(i0 < 0, np.float32(0), t)
+    i0 = np.clip(i0, 0, n_in - 1)
+    t = np.where(i0 >= n_in - 1, np.float32(0), t)
+    return i0, np.minimum(i0 + 1, n_in - 1), t.astype(np.float32)
+
+
 def resize_bilinear(img, new_w, new_h):
     """cv2.resize(img, (new_w, new_h)) with INTER_LINEAR for float images: source coordinate
     (x + 0.5) * (w / new_w) - 0.5, neighbours clamped to the image, separable lerp in float32."""
     img = np.asarray(img, np.float32)
     h, w = img.shape[:2]
-
-    def axis(n_out, n_in):
-        f = (np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5
-        i0 = np.floor(f)
-        t = (f - i0).astype(np.float32)
-        i0 = i0.astype(np.int64)
-        t = np.where(i0 < 0, np.float32(0), t)
-        i0 = np.clip(i0, 0, n_in - 1)
-        t = np.where(i0 >= n_in - 1, np.float32(0), t)
-        return i0, np.minimum(i0 + 1, n_in - 1), t.astype(np.float32)
-
-    x0, x1, tx = axis(int(new_w), w)
-    y0, y1, ty = axis(int(new_h), h)
+    x0, x1, tx = resize_axis(int(new_w), w)
+    y0, y1, ty = resize_axis(int(new_h), h)
     bx = tx.reshape((1, -1) + (1,) * (img.ndim - 2))
     by = ty.reshape((-1,) + (1,) * (img.ndim - 1))
     rows = img[:, x0] * (np.float32(1) - bx) + img[:, x1] * bx  # horizontal pass, then vertical
     return (rows[y0] * (np.float32(1) - by) + rows[y1] * by).astype(np.float32)
 
 
-def scale_mvs_input(img, intrinsics, max_w, max_h, base=32):
-    """general_eval.scale_mvs_input (:106-124): fit into (max_w, max_h) keeping the aspect ratio,
-    round both sides down to a multiple of `base`, rescale the intrinsics rows accordingly."""
-    h, w = img.shape[:2]
+def scale_mvs_camera(h, w, intrinsics, max_w, max_h, base=32):
+    """The size and intrinsics half of scale_mvs_input for an h x w image: (new_w, new_h, intrinsics)."""
     if h > max_h or w > max_w:
         scale = 1.0 * max_h / h
         if scale * w > max_w:
@@ -151,7 +152,15 @@ def scale_mvs_input(img, intrinsics, max_w, max_h, base=32):
     intrinsics = intrinsics.copy()
     intrinsics[0, :] *= 1.0 * new_w / w
     intrinsics[1, :] *= 1.0 * new_h / h
-    return resize_bilinear(img, int(new_w), int(new_h)), intrinsics
+    return int(new_w), int(new_h), intrinsics
+
+
+def scale_mvs_input(img, intrinsics, max_w, max_h, base=32):
+    """general_eval.scale_mvs_input (:106-124): fit into (max_w, max_h) keeping the aspect ratio,
+    round both sides down to a multiple of `base`, rescale the intrinsics rows accordingly."""
+    h, w = img.shape[:2]
+    new_w, new_h, intrinsics = scale_mvs_camera(h, w, intrinsics, max_w, max_h, base)
+    return resize_bilinear(img, new_w, new_h), intrinsics
 
 
 def _stack_sample(imgs, projs, depth_values, scan, ref_view):
