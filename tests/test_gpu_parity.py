@@ -237,13 +237,19 @@ def test_costregnet_matches_golden(model):
     assert np.abs(out - ref).max() <= 2e-5 * scale, (np.abs(out - ref).max(), scale)
 
 
-@pytest.mark.parametrize("layer,stride", [("conv1", 2), ("conv2", 1), ("conv3", 2), ("conv4", 1), ("conv5", 2),
-                                          ("conv6", 1)])
-def test_conv3d_layers(sd, model, layer, stride):
+# input depth 8 for every layer, then the depth each layer sees in a D = 8 stage (the Do <= 2 dispatch branches:
+# kd-skip conv3/conv6, conv4's second tile configuration, conv5's TAPOUT at one output slice)
+CONV3D_CASES = [("conv1", 2, 8), ("conv2", 1, 8), ("conv3", 2, 8), ("conv4", 1, 8), ("conv5", 2, 8), ("conv6", 1, 8),
+                ("conv2", 1, 4), ("conv3", 2, 4), ("conv4", 1, 2), ("conv5", 2, 2), ("conv6", 1, 1)]
+
+
+@pytest.mark.parametrize("layer,stride,depth", CONV3D_CASES,
+                         ids=[f"{l}-{s}" if d == 8 else f"{l}-{s}-d{d}" for l, s, d in CONV3D_CASES])
+def test_conv3d_layers(sd, model, layer, stride, depth):
     blk = getattr(model.cost_regularization[1], layer)
     w = blk.conv.weight.detach().cpu()
     co, ci = w.shape[:2]
-    x = torch.randn(1, ci, 8, 12, 20)
+    x = torch.randn(1, ci, depth, 12, 20)
     p = f"cost_regularization.1.{layer}."
     ref = F.relu(F.batch_norm(F.conv3d(x, w, stride=stride, padding=1), sd[p + "bn.running_mean"],
                               sd[p + "bn.running_var"], sd[p + "bn.weight"], sd[p + "bn.bias"], False, 0.1, 1e-5))

@@ -29,43 +29,20 @@ __device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
 // Weight-gradient grids of (pixel-range block, tap) pairs as a 1-D grid of xcd_range_tap_grid(ntaps, nblk)
 // blocks, dealt out so the ntaps blocks of one range share blockIdx % 8 -- one XCD, one L2: the taps
 // gather overlapping input neighbourhoods and the same output-gradient rows. false for padding blocks.
-#ifndef TMVS_WGRAD_XCD
-#define TMVS_WGRAD_XCD 1
-#endif
 __device__ __forceinline__ bool xcd_range_tap(int ntaps, int nblk, int& rb, int& k) {
-#if TMVS_WGRAD_XCD
   const int per = 8 * ntaps;
   const int grp = blockIdx.x / per, within = blockIdx.x % per;
   k = within / 8;
   rb = grp * 8 + within % 8;
   return rb < nblk;
-#else
-  (void)ntaps;
-  (void)nblk;
-  k = blockIdx.y;
-  rb = blockIdx.x;
-  return true;
-#endif
 }
-static inline dim3 xcd_range_tap_grid(int ntaps, int nblk) {
-  return TMVS_WGRAD_XCD ? dim3((unsigned)((nblk + 7) / 8 * 8 * ntaps)) : dim3((unsigned)nblk, (unsigned)ntaps);
-}
+static inline dim3 xcd_range_tap_grid(int ntaps, int nblk) { return dim3((unsigned)((nblk + 7) / 8 * 8 * ntaps)); }
 
 // (b, y, x) of row v of a [B][H][W] pixel grid, for a loader whose wave's rows all lie in the 64-row chunk
 // starting at v & ~63 (the weight-gradient reductions stage 64-row chunks from 64-aligned block starts):
 // the chunk start's coordinates by one scalar (wave-uniform) division, the row's by carrying from it --
 // instead of two divisions per lane and row
-#ifndef TMVS_CHUNK_COORDS
-#define TMVS_CHUNK_COORDS 1
-#endif
 __device__ __forceinline__ void chunk_row_coords(long v, int H, int W, int& b, int& y, int& x) {
-  if (!TMVS_CHUNK_COORDS) {
-    const long t = v / W;
-    x = (int)(v - t * W);
-    y = (int)(t % H);
-    b = (int)(t / H);
-    return;
-  }
   const long vl = v & ~63L;
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)vl);
   const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long)vl >> 32));
@@ -85,15 +62,6 @@ __device__ __forceinline__ void chunk_row_coords(long v, int H, int W, int& b, i
 
 // the same for row v of a [B][D][H][W] voxel grid: (b, z, y, x)
 __device__ __forceinline__ void chunk_row_coords3(long v, int D, int H, int W, int& b, int& z, int& y, int& x) {
-  if (!TMVS_CHUNK_COORDS) {
-    long t = v / W;
-    x = (int)(v - t * W);
-    y = (int)(t % H);
-    t /= H;
-    z = (int)(t % D);
-    b = (int)(t / D);
-    return;
-  }
   const long vl = v & ~63L;
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)vl);
   const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long)vl >> 32));
@@ -148,19 +116,17 @@ __device__ __forceinline__ double wave_xor_sum_dpp(double x) {
 // s + p[j0 * stride] + p[(j0 + step) * stride] + ... (j < n), added in that order in fp64 -- the partial
 // combines' fixed-order sums -- with 8 loads in flight ahead of their adds (a plain loop waits on each
 // load before its dependent add)
-#ifndef TMVS_SUM_BATCH
-#define TMVS_SUM_BATCH 8
-#endif
 template <typename T>
 __device__ __forceinline__ double strided_sum(const T* __restrict__ p, long j0, long n, long step, size_t stride,
                                               double s) {
+  constexpr int kBatch = 8;
   long j = j0;
-  for (; j + (TMVS_SUM_BATCH - 1) * step < n; j += TMVS_SUM_BATCH * step) {
-    T t[TMVS_SUM_BATCH];
+  for (; j + (kBatch - 1) * step < n; j += kBatch * step) {
+    T t[kBatch];
 #pragma unroll
-    for (int u = 0; u < TMVS_SUM_BATCH; ++u) t[u] = p[(size_t)(j + u * step) * stride];
+    for (int u = 0; u < kBatch; ++u) t[u] = p[(size_t)(j + u * step) * stride];
 #pragma unroll
-    for (int u = 0; u < TMVS_SUM_BATCH; ++u) s += (double)t[u];
+    for (int u = 0; u < kBatch; ++u) s += (double)t[u];
   }
   for (; j < n; j += step) s += (double)p[(size_t)j * stride];
   return s;
@@ -192,7 +158,7 @@ __device__ __forceinline__ floatx4_t buf_load_f32x4(__amdgpu_buffer_rsrc_t r, un
 // One pixel's softmax over D logits and winner-take-all (models/TransMVSNet.py:97-103,217-218):
 // prob = exp((x - max) - log(sum exp(x - max))) stored through put_prob(d, p); returns the first
 // maximum's index and its probability in best. Shared by softmax_wta_kernel (glue.hip) and the
-// fused prob_wta_kernel (costreg.hip) so both produce the same bits.
+// fused prob_wta_rows_kernel (costreg.hip) so both produce the same bits.
 template <int D, typename PutProb>
 __device__ __forceinline__ int softmax_first_max(const float (&x)[D], PutProb put_prob, float& best) {
   float m = x[0];

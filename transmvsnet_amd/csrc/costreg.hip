@@ -97,24 +97,13 @@ __device__ __forceinline__ float act(float v, float lo) { return v > lo ? v : lo
 // its NBW = TD*TH/4 rows through the 27 taps: A (weights) from global/L2, requested two taps
 // ahead, B from LDS. The next chunk's tile is fetched into registers during the current
 // chunk's MFMAs.
-#ifndef TMVS_LDS_BPF
-#define TMVS_LDS_BPF 1
-#endif
-#ifndef TMVS_LDS_ABL
-#define TMVS_LDS_ABL 0  // timing ablations (scripts/gpu/r17f.sh): 1 no weight loads, 2 no next-chunk fetch,
-#endif                  // 4 no chunk barriers / commit, 8 no MFMAs -- wrong results, never the product
-#ifndef TMVS_LDS_SGB
-#define TMVS_LDS_SGB 1
-#endif
-// TAPOUT: every channel chunk's tile is staged at once and the K walk runs taps outer, chunks inner --
-// conv3d_direct_kernel's order (tap, chunk, lane channel), so the sums are that kernel's bit for bit; the
-// default walks chunks outer (one chunk's tile in LDS at a time), which re-associates the K sum when
-// CIN > 16. TAPOUT needs TD = 1 (the kd slices in the depth padding are skipped per workgroup, exact zeros).
+// TAPOUT: every channel chunk's tile is staged at once and the K walk runs taps outer, channel chunks
+// inner -- K order (tap, chunk, lane channel), the order the oracle-parity tests pin; the default walks
+// chunks outer (one chunk's tile in LDS at a time), which re-associates the K sum when CIN > 16.
+// TAPOUT needs TD = 1 (the kd slices in the depth padding are skipped per workgroup, exact zeros).
+constexpr int kLdsWavesPerEu = 3;
 template <int CIN, int COUT, int S, int TD, int TH, int MBB, int WS = 1, bool KDSKIP = false, bool TAPOUT = false>
-#ifndef TMVS_LDS_WPE
-#define TMVS_LDS_WPE 3
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMVS_LDS_WPE, TMVS_LDS_WPE))) void conv3d_lds_kernel(const float* __restrict__ x, const float* __restrict__ wpk,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLdsWavesPerEu, kLdsWavesPerEu))) void conv3d_lds_kernel(const float* __restrict__ x, const float* __restrict__ wpk,
                                                          const float* __restrict__ alpha,
                                                          const float* __restrict__ shift, float* __restrict__ y,
                                                          Geo g) {
@@ -210,16 +199,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMVS_LDS_WP
 #pragma unroll
     for (int m = 0; m < MBW; ++m) {
       const int co = (mb0 + m) * 16 + col;  // channels >= COUT read zeros
-      if (TMVS_LDS_ABL & 1) {  // timing ablation only: no weight loads
-#pragma unroll
-        for (int i = 0; i < PL; ++i) a[m].v[i] = (float)(tap * PL + i + ch) * 1e-3f;
-        continue;
-      }
       buf_load(a[m], wb, (co < COUT ? co * CIN + kgrp * PL : Buf::kOOB / 4) * 4, (tap * COUT * CIN + ch * CK) * 4);
     }
   };
   VecN<PL> aw[3][MBW];
-  // one tap: B fragments from the LDS tile, NBW x MBB x PL MFMAs
   // B fragments of one tap from the LDS tile
   auto bload_at = [&](const float* base, int kd, int kh, int kw, VecN<PL>(&b)[NBW]) {
 #pragma unroll
@@ -234,13 +217,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMVS_LDS_WP
   auto bload = [&](int kd, int kh, int kw, VecN<PL>(&b)[NBW]) { bload_at(tile, kd, kh, kw, b); };
   // one tap: NBW x MBB x PL MFMAs on fragments already in registers
   auto tap_mfma = [&](const VecN<PL>* a, const VecN<PL>* b) {
-    if (TMVS_LDS_ABL & 8) {  // timing ablation only: no MFMAs (one FMA keeps the loads live)
-#pragma unroll
-      for (int r = 0; r < NBW; ++r)
-#pragma unroll
-        for (int m = 0; m < MBW; ++m) acc[r][m][0] = fmaf(a[m].v[0], b[r].v[0], acc[r][m][0]);
-      return;
-    }
 #pragma unroll
     for (int j = 0; j < PL; ++j)
 #pragma unroll
@@ -251,13 +227,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMVS_LDS_WP
     // one-MFMA schedule groups keep the accumulators' chains interleaved as written (the scheduler
     // otherwise issued each accumulator's PL dependent MFMAs back to back: 40-cycle dependent issue
     // against 32 for an independent one)
-    if constexpr (TMVS_LDS_SGB)
 #pragma unroll
-      for (int i = 0; i < PL * NBW * MBW; ++i) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    for (int i = 0; i < PL * NBW * MBW; ++i) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
     __builtin_amdgcn_sched_barrier(0);  // keep the lookahead schedule (and the VGPR budget)
   };
-  // B of tap t + 1 is read from LDS before tap t's MFMAs (TMVS_LDS_BPF; read right before its own
-  // MFMAs its latency sat between every tap's MFMA groups)
+  // B of tap t + 1 is read from LDS before tap t's MFMAs (read right before its own MFMAs its
+  // latency sat between every tap's MFMA groups)
   VecN<PL> bw[2][NBW];
   if constexpr (TAPOUT) {
     // all chunks staged (every chunk's loads in flight before the first commit), then per kept kd slice
@@ -329,10 +304,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMVS_LDS_WP
             else if (MORE)
               wload(ch + 1, kd_lo * 9 + k9 - 7, aw[(k9 + 2) % 3]);
           }
-          if (MORE && !(TMVS_LDS_ABL & 2) && k9 == 6 && kd == kd_hi) fetch(ch + 1);
+          if (MORE && k9 == 6 && kd == kd_hi) fetch(ch + 1);
           // B prefetch within the slice (9 taps: the parity would flip across the rolled kd loop)
-          if (!TMVS_LDS_BPF || k9 == 0) bload(kd, k9 / 3, k9 % 3, bw[k9 & 1]);
-          if (TMVS_LDS_BPF && k9 + 1 < 9) bload(kd, (k9 + 1) / 3, (k9 + 1) % 3, bw[(k9 + 1) & 1]);
+          if (k9 == 0) bload(kd, k9 / 3, k9 % 3, bw[k9 & 1]);
+          if (k9 + 1 < 9) bload(kd, (k9 + 1) / 3, (k9 + 1) % 3, bw[(k9 + 1) & 1]);
           tap_mfma(aw[k9 % 3], bw[k9 & 1]);
         }
     } else {
@@ -342,13 +317,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMVS_LDS_WP
           wload(ch, tap + 2, aw[(tap + 2) % 3]);
         else if (MORE)
           wload(ch + 1, tap - 25, aw[(tap + 2) % 3]);
-        if (MORE && !(TMVS_LDS_ABL & 2) && tap == 24) fetch(ch + 1);
-        if (!TMVS_LDS_BPF || tap == 0) bload(tap / 9, (tap / 3) % 3, tap % 3, bw[tap & 1]);
-        if (TMVS_LDS_BPF && tap + 1 < 27) bload((tap + 1) / 9, ((tap + 1) / 3) % 3, (tap + 1) % 3, bw[(tap + 1) & 1]);
+        if (MORE && tap == 24) fetch(ch + 1);
+        if (tap == 0) bload(tap / 9, (tap / 3) % 3, tap % 3, bw[tap & 1]);
+        if (tap + 1 < 27) bload((tap + 1) / 9, ((tap + 1) / 3) % 3, (tap + 1) % 3, bw[(tap + 1) & 1]);
         tap_mfma(aw[tap % 3], bw[tap & 1]);
       }
     }
-    if (MORE && !(TMVS_LDS_ABL & 4)) {
+    if (MORE) {
       __syncthreads();
       commit();
       __syncthreads();
@@ -382,119 +357,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMVS_LDS_WP
   }
 }
 
-// ---------------------------------------------------------------- conv3d, direct (no LDS)
-// Used for the stride-2 layers: no LDS footprint, high occupancy hides the per-tap L1/L2 latency.
-// (Branch-free buffer loads with a one-step-ahead register prefetch measured the same, r17a.)
-template <int CIN, int COUT, int S, int NBW, int MBW>
-__global__ __launch_bounds__(256) void conv3d_direct_kernel(const float* __restrict__ x, const float* __restrict__ wpk,
-                                                          const float* __restrict__ alpha,
-                                                          const float* __restrict__ shift, float* __restrict__ y,
-                                                          Geo g, int n_tasks) {
-  constexpr int CK = CIN < 16 ? CIN : 16;  // channels per K chunk
-  constexpr int PL = CK / 4;               // channels per lane per chunk (= MFMAs per chunk)
-  constexpr int MB = (COUT + 15) / 16;     // 16-channel output blocks
-  constexpr int MG = MB / MBW;             // wave groups along cout
-  static_assert(MB % MBW == 0, "MBW must divide MB");
-  const int lane = threadIdx.x & 63;
-  const int task = xcd_remap(blockIdx.x, gridDim.x) * 4 + (threadIdx.x >> 6);
-  if (task >= n_tasks) return;
-  // task -> (mg fastest, wseg, hgrp, od, n)
-  int t = task;
-  const int mg = t % MG;
-  t /= MG;
-  const int nws = (g.Wo + 15) / 16;
-  const int wseg = t % nws;
-  t /= nws;
-  const int nhg = (g.Ho + NBW - 1) / NBW;
-  const int hg = t % nhg;
-  t /= nhg;
-  const int od = t % g.Do;
-  const int n = t / g.Do;
-
-  const int col = lane & 15;
-  const int kgrp = lane >> 4;
-  const int ow = wseg * 16 + col;
-  const size_t in_n = (size_t)n * g.Di * g.Hi * g.Wi;
-
-  floatx4 acc[NBW][MBW];
-#pragma unroll
-  for (int r = 0; r < NBW; ++r)
-#pragma unroll
-    for (int m = 0; m < MBW; ++m) acc[r][m] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-  for (int kd = 0; kd < 3; ++kd) {
-    const int id = od * S - 1 + kd;
-    if (id < 0 || id >= g.Di) continue;  // wave-uniform
-    for (int kh = 0; kh < 3; ++kh) {
-      for (int kw = 0; kw < 3; ++kw) {
-        const int tap = kd * 9 + kh * 3 + kw;
-        const int iw = ow * S - 1 + kw;
-        const bool wok = iw >= 0 && iw < g.Wi && ow < g.Wo;
-#pragma unroll
-        for (int ch = 0; ch < CIN / CK; ++ch) {
-          const int cbase = ch * CK + kgrp * PL;
-          VecN<PL> a[MBW];
-#pragma unroll
-          for (int m = 0; m < MBW; ++m) {
-            const int co = (mg * MBW + m) * 16 + col;
-            if (co < COUT)
-              a[m].load(wpk + ((size_t)tap * COUT + co) * CIN + cbase);
-            else
-              a[m].zero();
-          }
-          VecN<PL> b[NBW];
-#pragma unroll
-          for (int r = 0; r < NBW; ++r) {
-            const int oh = hg * NBW + r;
-            const int ih = oh * S - 1 + kh;
-            if (wok && oh < g.Ho && ih >= 0 && ih < g.Hi)
-              b[r].load(x + (in_n + ((size_t)id * g.Hi + ih) * g.Wi + iw) * CIN + cbase);
-            else
-              b[r].zero();
-          }
-#pragma unroll
-          for (int j = 0; j < PL; ++j)
-#pragma unroll
-            for (int r = 0; r < NBW; ++r)
-#pragma unroll
-              for (int m = 0; m < MBW; ++m)
-                acc[r][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].v[j], b[r].v[j], acc[r][m], 0, 0, 0);
-        }
-      }
-    }
-  }
-  // epilogue: lane holds couts 4*kgrp..+3 of block m for voxel `col`
-  if (ow >= g.Wo) return;
-  const size_t out_n = (size_t)n * g.Do * g.Ho * g.Wo;
-#pragma unroll
-  for (int m = 0; m < MBW; ++m) {
-    const int co = (mg * MBW + m) * 16 + kgrp * 4;
-    if (co >= COUT) continue;
-    const float4 al = *reinterpret_cast<const float4*>(alpha + co);
-    const float4 sh = *reinterpret_cast<const float4*>(shift + co);
-#pragma unroll
-    for (int r = 0; r < NBW; ++r) {
-      const int oh = hg * NBW + r;
-      if (oh >= g.Ho) continue;
-      float4 o;
-      o.x = act(fmaf(acc[r][m][0], al.x, sh.x), g.lo);
-      o.y = act(fmaf(acc[r][m][1], al.y, sh.y), g.lo);
-      o.z = act(fmaf(acc[r][m][2], al.z, sh.z), g.lo);
-      o.w = act(fmaf(acc[r][m][3], al.w, sh.w), g.lo);
-      *reinterpret_cast<float4*>(y + (out_n + ((size_t)od * g.Ho + oh) * g.Wo + ow) * COUT + co) = o;
-    }
-  }
-}
-
 // ---------------------------------------------------------------- ConvTranspose3d k3 s2 p1 op1
 // output o = 2i - 1 + k: parity 0 -> (k=1, i=o/2); parity 1 -> (k=0, i=o/2+1), (k=2, i=o/2).
 // Workgroup tile in input-grid coordinates: 16 columns x THI rows x TDI slices (outputs
 // 32 x 2THI x 2TDI). Each wave owns TDI*THI/4 input-grid rows and all 8 output parity
 // classes of them (a class = 16 outputs with one parity per dimension = one tap set of
 // 1, 2, 4 or 8 taps), so the waves carry equal work. Input tile (+1 halo) staged in LDS.
-#ifndef TMVS_DECONV_ABL
-#define TMVS_DECONV_ABL 0  // timing ablations (wrong results): 1 no weight staging, 2 no tile staging, 4 no MFMAs
-#endif
 template <int CIN, int COUT, int TDI, int THI, int MBB>
 __global__ __launch_bounds__(256) void deconv3d_lds_kernel(const float* __restrict__ x,
                                                            const float* __restrict__ wpk,
@@ -508,7 +376,7 @@ __global__ __launch_bounds__(256) void deconv3d_lds_kernel(const float* __restri
   constexpr int MG = MB / MBB;
   constexpr int NBW = TDI * THI / 4;
   constexpr int LW = 17, LH = THI + 1, LD = TDI + 1;
-  constexpr bool SWZ = (CK == 16);  // (stride 2 included: conv3's instance)  // conflict-free ds_read_b128 (see conv3d_lds_kernel)
+  constexpr bool SWZ = (CK == 16);  // conflict-free ds_read_b128 (see conv3d_lds_kernel)
   constexpr int VST = SWZ ? 16 : CK + 4;
   constexpr int NVOX = LD * LH * LW;
   static_assert(MB % MBB == 0 && (TDI * THI) % 4 == 0, "tile");
@@ -546,7 +414,7 @@ __global__ __launch_bounds__(256) void deconv3d_lds_kernel(const float* __restri
 #pragma unroll 1
   for (int ch = 0; ch < CIN / CK; ++ch) {
     if (ch) __syncthreads();
-    for (int idx = threadIdx.x; idx < ((TMVS_DECONV_ABL & 2) ? 0 : NVOX * PL); idx += 256) {
+    for (int idx = threadIdx.x; idx < NVOX * PL; idx += 256) {
       const int vox = idx / PL, q = idx - vox * PL;
       const int lw = vox % LW, rest = vox / LW, lh = rest % LH, ld = rest / LH;
       const int iw = mw0 + lw, ih = mh0 + lh, id = md0 + ld;
@@ -556,7 +424,7 @@ __global__ __launch_bounds__(256) void deconv3d_lds_kernel(const float* __restri
       const int qs = SWZ ? (q ^ ((vox >> 1) & 3)) : q;
       *reinterpret_cast<float4*>(tile + vox * VST + 4 * qs) = v;
     }
-    for (int idx = threadIdx.x; idx < ((TMVS_DECONV_ABL & 1) ? 0 : 27 * RM * 4); idx += 256) {
+    for (int idx = threadIdx.x; idx < 27 * RM * 4; idx += 256) {
       const int q = idx & 3, row = (idx >> 2) % RM, tap = (idx >> 2) / RM;
       const float4 v = *reinterpret_cast<const float4*>(wpk + ((size_t)tap * COUT + mg * 16 + row) * CIN + ch * CK + 4 * q);
       *reinterpret_cast<float4*>(wts + (tap * RM + row) * 16 + 4 * (q ^ ((row >> 1) & 3))) = v;
@@ -591,12 +459,8 @@ __global__ __launch_bounds__(256) void deconv3d_lds_kernel(const float* __restri
 #pragma unroll
               for (int j = 0; j < PL; ++j)
 #pragma unroll
-                for (int m = 0; m < MBB; ++m) {
-                  if (TMVS_DECONV_ABL & 4)  // timing ablation: no MFMAs (one FMA keeps the reads live)
-                    acc[r][cls][m][0] = fmaf(a[m].v[j], b.v[j], acc[r][cls][m][0]);
-                  else
-                    acc[r][cls][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].v[j], b.v[j], acc[r][cls][m], 0, 0, 0);
-                }
+                for (int m = 0; m < MBB; ++m)
+                  acc[r][cls][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].v[j], b.v[j], acc[r][cls][m], 0, 0, 0);
             }
           }
     }
@@ -786,111 +650,32 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x,
 }
 
 // ---------------------------------------------------------------- prob: 8 -> 1, VALU
-// A wave owns one (h) row segment of 62 output columns; lane l holds column w0 + l - 1 (lanes
-// 0 and 63 are the kw halo and write nothing). Every input row is one coalesced 32-byte load
-// per lane (the segment's 64 pixels are 2 KB contiguous); the kw = 0 / 2 neighbours come from
-// lanes l -+ 1 by wave-wide DPP shifts instead of re-gathering them (the 3x re-read of the
+// A wave owns NR consecutive rows of one segment of 62 output columns; lane l holds column
+// w0 + l - 1 (lanes 0 and 63 are the kw halo and write nothing). Every input row is one coalesced
+// 32-byte load per lane (the segment's 64 pixels are 2 KB contiguous); the kw = 0 / 2 neighbours come
+// from lanes l -+ 1 by wave-wide DPP shifts instead of re-gathering them (the 3x re-read of the
 // 1-pixel-per-thread form made this kernel address-unit bound). The thread walks kDChunk output
-// planes (prob_walk).
+// planes (prob_walk_rows).
 
-// The D walk both prob kernels run: input plane i (3 rows x 3 taps x 8 channels) feeds outputs
-// i+1 (kd=0), i (kd=1) and i-1 (kd=2), each output's FMA chain in (kd, kh, kw, c) order:
+// The D walk both prob kernels run, for the NR output rows h .. h+NR-1 of a wave: input plane i
+// (NR+2 rows x 3 taps x 8 channels) feeds outputs i+1 (kd=0), i (kd=1) and i-1 (kd=2), each output's
+// FMA chain in (kd, kh, kw, c) order:
 // c12 = {output i (kd=0 done, adds kd=1), output i-1 (kd=0,1 done, adds kd=2)}, one packed FMA per
 // (tap, channel) with the weight pair {W[kd=1], W[kd=2]} (an aligned SGPR pair, see the host
 // packing in include/transmvs.h) and x broadcast; acc_next (output i+1, kd=0) is scalar.
-// Planes d0-1 .. d0+8 (kDChunk + 2), double-buffered: plane i+1's three rows are in flight while
-// plane i is consumed (with one row of lookahead a wave had a single load outstanding and the
-// kernels ran at 2.3-2.5 TB/s). emit(d, logit) for d = d0 .. d0+7 (the caller bounds d by D).
-// the same for prob_walk's plane loop (prob_kernel, stage 1: 38.6 -> 37.2 us, bitwise the same, r18z2)
-#ifndef TMVS_PROB1_UNIFORM
-#define TMVS_PROB1_UNIFORM 1
-#endif
-template <typename Emit>
-__device__ __forceinline__ void prob_walk(__amdgpu_buffer_rsrc_t rx, int w, int h, int D, int H, int W, int d0,
-                                          const float* __restrict__ wt, Emit emit) {
-  const unsigned offw = (unsigned)w < (unsigned)W ? (unsigned)w * 32u : kOffOut;
-  auto load_plane = [&](int i, float4 (&o)[3][2]) {
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-      const int ih = h - 1 + kh;
-      const unsigned offr = ((unsigned)i < (unsigned)D && (unsigned)ih < (unsigned)H)
-                                ? ((unsigned)i * (unsigned)H + (unsigned)ih) * (unsigned)W * 32u
-                                : kOffOut;
-      const unsigned off = (offr + offw) | ((offr | offw) & kOffOut);
-      const floatx4 u = buf_load_f32x4(rx, off);
-      const floatx4 v = buf_load_f32x4(rx, off + 16u);
-      o[kh][0] = make_float4(u[0], u[1], u[2], u[3]);
-      o[kh][1] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  };
-  float2_v c12 = {0.f, 0.f};
-  auto plane = [&](int i, const float4 (&p)[3][2]) {
-    float acc_next = 0.f;
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-      const float xc[8] = {p[kh][0].x, p[kh][0].y, p[kh][0].z, p[kh][0].w,
-                           p[kh][1].x, p[kh][1].y, p[kh][1].z, p[kh][1].w};
-      // the row's 72 weights through an opaque (uniform) offset: loaded where the row is consumed
-      // instead of all 216 hoisted out of the plane loop into SGPRs (spills)
-      int wo = kh * 72;
-      asm volatile("" : "+s"(wo));
-      const float* wk = wt + __builtin_amdgcn_readfirstlane(wo);
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const float xv = kw == 0 ? lane_from_left(xc[c]) : kw == 1 ? xc[c] : lane_from_right(xc[c]);
-          const float2_v wp = *reinterpret_cast<const float2_v*>(wk + 2 * (kw * 8 + c));
-          acc_next = fmaf(wk[48 + kw * 8 + c], xv, acc_next);
-          c12 = __builtin_elementwise_fma(wp, float2_v{xv, xv}, c12);
-        }
-      }
-      // both chains complete per row (no FMA sunk past the row: its shifted taps die here)
-      asm volatile("" : "+v"(acc_next), "+v"(c12));
-    }
-    if (i - 1 >= d0) emit(i - 1, c12.y);  // output i-1 complete
-    c12 = float2_v{acc_next, c12.x};
-  };
-  float4 pa[3][2], pb[3][2];
-#if TMVS_PROB1_UNIFORM
-  d0 = __builtin_amdgcn_readfirstlane(d0);  // as in prob_walk_rows (TMVS_PROB_UNIFORM)
-#endif
-  load_plane(d0 - 1, pa);
-#if TMVS_PROB1_UNIFORM
-#pragma unroll
-  for (int j = 0; j < kDChunk + 2; j += 2) {
-    const int i = d0 - 1 + j;
-#else
-#pragma unroll 1
-  for (int i = d0 - 1; i < d0 + kDChunk + 1; i += 2) {  // planes i (in pa) and i + 1 (in pb)
-#endif
-    load_plane(i + 1, pb);
-    plane(i, pa);
-    load_plane(i + 2, pa);  // (past the last plane: rows the next chunk reads anyway)
-    plane(i + 1, pb);
-  }
-}
-
-// prob_walk_rows' plane loop: 0 = divergent loop on the per-lane d0 (the latch copied the prefetched
-// plane between buffers after a vmcnt(0)), 1 = d0 made wave-uniform, 2 = uniform and fully unrolled
-// (r18z, bitwise the same: stage 3 89.6 -> 86.0 us, stage 2 94.7 -> 93.5 us; 1 alone 89.8 / 96.3; the
-// same build re-run on another box in r18z2: 89.2 / 93.0 -- box-to-box spread of about 3 %)
-#ifndef TMVS_PROB_UNIFORM
-#define TMVS_PROB_UNIFORM 2
-#endif
-// prob_walk for NR consecutive output rows h .. h+NR-1 per wave: input plane i's rows h-1 .. h+NR are
-// loaded once (NR+2 row loads per plane instead of 3 NR: the row re-reads had the kernels address-unit
-// bound) and each row feeds the outputs it borders. Every output keeps prob_walk's FMA chains and
-// order (kd, kh, kw, c), so the logits are bitwise prob_walk's. emit(r, d, logit).
+// Plane i's rows h-1 .. h+NR are loaded once (NR+2 row loads per plane instead of 3 NR: the row
+// re-reads had the kernels address-unit bound) and each row feeds the outputs it borders, so the
+// logits do not depend on NR.
+// Planes d0-1 .. d0+8 (kDChunk + 2), double-buffered: plane i+1's rows are in flight while plane i
+// is consumed (with one row of lookahead a wave had a single load outstanding and the kernels ran at
+// 2.3-2.5 TB/s). emit(r, d, logit) for d = d0 .. d0+7 (the caller bounds d by D).
 template <int NR, typename Emit>
 __device__ __forceinline__ void prob_walk_rows(__amdgpu_buffer_rsrc_t rx, int w, int h, int D, int H, int W, int d0,
                                                const float* __restrict__ wt, Emit emit) {
   constexpr int NL = NR + 2;
-#if TMVS_PROB_UNIFORM
   // d0 is the wave's depth chunk: wave-uniform, but derived from threadIdx.x, so without this the plane
   // loop is a divergent (exec-mask) loop whose latch waits vmcnt(0) for the prefetched plane
   d0 = __builtin_amdgcn_readfirstlane(d0);
-#endif
   const unsigned offw = (unsigned)w < (unsigned)W ? (unsigned)w * 32u : kOffOut;
   auto load_plane = [&](int i, float4 (&o)[NL][2]) {
 #pragma unroll
@@ -915,6 +700,8 @@ __device__ __forceinline__ void prob_walk_rows(__amdgpu_buffer_rsrc_t rx, int w,
     for (int r = 0; r < NR; ++r) acc_next[r] = 0.f;
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh) {
+      // the row's 72 weights through an opaque (uniform) offset: loaded where the row is consumed
+      // instead of all 216 hoisted out of the plane loop into SGPRs (spills)
       int wo = kh * 72;
       asm volatile("" : "+s"(wo));
       const float* wk = wt + __builtin_amdgcn_readfirstlane(wo);
@@ -932,47 +719,33 @@ __device__ __forceinline__ void prob_walk_rows(__amdgpu_buffer_rsrc_t rx, int w,
             c12[r] = __builtin_elementwise_fma(wp, float2_v{xv, xv}, c12[r]);
           }
         }
+        // both chains complete per row (no FMA sunk past the row: its shifted taps die here)
         asm volatile("" : "+v"(acc_next[r]), "+v"(c12[r]));
       }
     }
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
-      if (i - 1 >= d0) emit(r, i - 1, c12[r].y);
+      if (i - 1 >= d0) emit(r, i - 1, c12[r].y);  // output i-1 complete
       c12[r] = float2_v{acc_next[r], c12[r].x};
     }
   };
   float4 pa[NL][2], pb[NL][2];
   load_plane(d0 - 1, pa);
-#if TMVS_PROB_UNIFORM >= 2
   // unrolled: no loop-carried plane buffers, whose register copies at the latch waited vmcnt(0)
 #pragma unroll
   for (int j = 0; j < kDChunk + 2; j += 2) {
-    const int i = d0 - 1 + j;
-#else
-#pragma unroll 1
-  for (int i = d0 - 1; i < d0 + kDChunk + 1; i += 2) {
-#endif
+    const int i = d0 - 1 + j;  // planes i (in pa) and i + 1 (in pb)
     load_plane(i + 1, pb);
     plane(i, pa);
-    load_plane(i + 2, pa);
+    load_plane(i + 2, pa);  // (past the last plane: rows the next chunk reads anyway)
     plane(i + 1, pb);
   }
 }
 
-// rows per wave of the raw prob walk (prob_kernel: 1; the 2-row form measured 42.3 -> 44.9 us at stage 1's
-// D = 48, 96.0 -> 92.1 / 90.9 -> 87.8 at stages 2 / 3, r16c) and of the fused prob + softmax/WTA kernel
-// (stages 2 / 3)
-#ifndef TMVS_PROB_ROWS
-#define TMVS_PROB_ROWS 1
-#endif
-#ifndef TMVS_PROB_WTA_ROWS
-#define TMVS_PROB_WTA_ROWS 2
-#endif
-
-// prob_kernel with NR output rows per wave (4 waves: 4 NR rows per workgroup)
+// raw logits, NR output rows per wave (4 waves: 4 NR rows per workgroup), one depth chunk per workgroup
 template <int NR>
-__global__ __launch_bounds__(256) void prob_rows_kernel(const float* __restrict__ x, float* __restrict__ y, int D, int H,
-                                                        int W, const float* __restrict__ wt) {
+__global__ __launch_bounds__(256) void prob_kernel(const float* __restrict__ x, float* __restrict__ y, int D, int H,
+                                                   int W, const float* __restrict__ wt) {
   const int HW = H * W;
   const int nseg = (W + kProbCols - 1) / kProbCols, nrow = (H + 4 * NR - 1) / (4 * NR), ndc = (D + kDChunk - 1) / kDChunk;
   int lb = xcd_remap(blockIdx.x, gridDim.x);
@@ -995,8 +768,15 @@ __global__ __launch_bounds__(256) void prob_rows_kernel(const float* __restrict_
   });
 }
 
-// prob_wta_kernel with NR rows per workgroup: wave k walks depth chunk k of all NR rows; after the
-// barrier the first waves run the softmax / WTA of one row each (wave 0 of all rows when D = 8)
+// ---------------------------------------------------------------- prob + softmax / WTA, fused
+// prob_kernel's row-segment D walk with the D / 8 depth chunks of NR rows of one segment as the waves
+// of one workgroup (wave k walks planes 8k-1 .. 8k+8 of all NR rows, exactly prob_kernel's chunk k);
+// each wave parks its 8 logits per column in LDS ([NR][D][64]) instead of HBM, and after one barrier
+// the first waves run softmax_first_max (common.h, the code softmax_wta_kernel runs) per column of one
+// row each (wave 0 of all rows when D = 8) and gather the winning hypothesis
+// (models/TransMVSNet.py:97-103,217-221). Same FMA chains as prob_kernel, so prob / depth / conf equal
+// prob_kernel + softmax_wta_kernel bit for bit, without the logits' 8·D bytes per pixel of HBM traffic
+// and one launch.
 template <int D, int NR>
 __global__ __launch_bounds__(64 * (D / kDChunk)) void prob_wta_rows_kernel(
     const float* __restrict__ x, const float* __restrict__ wt, const float* __restrict__ hyp, int H, int W, float lo,
@@ -1036,87 +816,18 @@ __global__ __launch_bounds__(64 * (D / kDChunk)) void prob_wta_rows_kernel(
   }
 }
 
-__global__ __launch_bounds__(256) void prob_kernel(const float* __restrict__ x, float* __restrict__ y, int D, int H,
-                                                   int W, const float* __restrict__ wt) {
-  const int HW = H * W;
-  const int nseg = (W + kProbCols - 1) / kProbCols, nrow = (H + 3) / 4, ndc = (D + kDChunk - 1) / kDChunk;
-  int lb = xcd_remap(blockIdx.x, gridDim.x);
-  const int seg = lb % nseg;
-  lb /= nseg;
-  const int rowb = lb % nrow;
-  lb /= nrow;
-  const int dc = lb % ndc;
-  const int n = lb / ndc;
-  const int lane = threadIdx.x & 63;
-  const int h = rowb * 4 + (threadIdx.x >> 6);
-  if (h >= H) return;  // whole wave
-  const int w = seg * kProbCols + lane - 1;
-  const bool writes = lane >= 1 && lane <= kProbCols && w < W;
-  const int d0 = dc * kDChunk, d1 = min(D, d0 + kDChunk);
-  const __amdgpu_buffer_rsrc_t rx = raw_rsrc(x + (size_t)n * D * HW * 8, (unsigned)(D * HW * 32));
-  float* yn = y + (size_t)n * D * HW + (size_t)h * W + w;
-  prob_walk(rx, w, h, D, H, W, d0, wt, [&](int d, float v) {
-    if (d < d1 && writes) yn[(size_t)d * HW] = v;
-  });
-}
-
-// ---------------------------------------------------------------- prob + softmax / WTA, fused
-// prob_kernel's row-segment D walk with the D / 8 depth chunks of one row segment as the waves of
-// one workgroup (wave k walks planes 8k-1 .. 8k+8, exactly prob_kernel's chunk k); each wave parks
-// its 8 logits per column in LDS ([D][64]) instead of HBM, and after one barrier wave 0 runs
-// softmax_first_max (common.h, the code softmax_wta_kernel runs) per column and gathers the
-// winning hypothesis (models/TransMVSNet.py:97-103,217-221). Same FMA chains as prob_kernel, so
-// prob / depth / conf equal prob_kernel + softmax_wta_kernel bit for bit, without the logits'
-// 8·D bytes per pixel of HBM traffic and one launch; same wave count as prob_kernel.
-template <int D>
-__global__ __launch_bounds__(64 * (D / kDChunk)) void prob_wta_kernel(
-    const float* __restrict__ x, const float* __restrict__ wt, const float* __restrict__ hyp, int H, int W, float lo,
-    float hi, float* __restrict__ prob, float* __restrict__ depth, float* __restrict__ depth_raw,
-    float* __restrict__ conf) {
-  __shared__ float lg[D * 64];
-  const int HW = H * W;
-  const int nseg = (W + kProbCols - 1) / kProbCols;
-  int lb = xcd_remap(blockIdx.x, gridDim.x);
-  const int seg = lb % nseg;
-  lb /= nseg;
-  const int h = lb % H;
-  const int n = lb / H;
-  const int lane = threadIdx.x & 63;
-  const int d0 = (threadIdx.x >> 6) * kDChunk;
-  const int w = seg * kProbCols + lane - 1;
-  const bool writes = lane >= 1 && lane <= kProbCols && w < W;
-  const __amdgpu_buffer_rsrc_t rx = raw_rsrc(x + (size_t)n * D * HW * 8, (unsigned)(D * HW * 32));
-  prob_walk(rx, w, h, D, H, W, d0, wt, [&](int d, float v) { lg[d * 64 + lane] = v; });
-  __syncthreads();
-  if (threadIdx.x >= 64 || !writes) return;
-  float xl[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) xl[d] = lg[d * 64 + lane];
-  const size_t base = (size_t)n * D * HW + (size_t)h * W + w;
-  float best;
-  const int bi = softmax_first_max<D>(xl, [&](int d, float pr) { prob[base + (size_t)d * HW] = pr; }, best);
-  const size_t o = (size_t)n * HW + (size_t)h * W + w;
-  const float dr = hyp[base + (size_t)bi * HW];
-  depth_raw[o] = dr;
-  depth[o] = fminf(fmaxf(dr, lo), hi);
-  conf[o] = best;
-}
-
-
 // ---------------------------------------------------------------- conv 16 -> 16, stride 1 (conv2)
 // Persistent form of conv3d_lds_kernel for the one stride-1 layer whose weights fit in LDS next
 // to a tile (27 x 16 x 16 fp32 = 27 KB): a workgroup stages them once, then walks its share of
 // 2x4x16-voxel output tiles; the next tile's input is fetched into registers while the
 // current tile's 27 taps run on the MFMAs, and committed to LDS between two barriers.
 // Same fragment layouts, tap order and epilogue as conv3d_lds_kernel.
-// NWV waves per workgroup (4, or 8 = two workgroups' rows in one: the staged weights shared by twice
-// the waves, 4 waves/SIMD at <= 128 VGPRs instead of 2 workgroups x 4 waves at 2 waves/SIMD)
-template <int TD, int TH, int NWV = 4>
-__global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV == 8 ? 4 : 2))) void conv3d_c16_kernel(const float* __restrict__ x, const float* __restrict__ wpk,
+template <int TD, int TH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv3d_c16_kernel(const float* __restrict__ x, const float* __restrict__ wpk,
                                                          const float* __restrict__ alpha,
                                                          const float* __restrict__ shift, float* __restrict__ y, Geo g,
                                                          int ntiles) {
-  constexpr int C = 16, PL = 4, NBW = TD * TH / NWV, NTH = NWV * 64;
+  constexpr int C = 16, PL = 4, NWV = 4, NBW = TD * TH / NWV, NTH = NWV * 64;  // 4 waves per workgroup
   static_assert(TD * TH % NWV == 0, "rows split evenly over the waves");
   constexpr int LW = 18, LH = TH + 2, LD = TD + 2, VST = 16;
   constexpr int NVOX = LD * LH * LW;
@@ -1226,9 +937,9 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
   }
 }
 
-// residency of a persistent kernel: resident workgroups per CU x CUs (queried once per kernel)
+// residency of a persistent kernel (256 threads): resident workgroups per CU x CUs (queried once per kernel)
 template <typename K>
-static int persistent_grid(K kernel, long ntiles, int block = 256) {
+static int persistent_grid(K kernel, long ntiles) {
   struct Entry {
     const void* fn;
     int dev, cap;
@@ -1241,23 +952,18 @@ static int persistent_grid(K kernel, long ntiles, int block = 256) {
     if (cache[i].fn == (const void*)kernel && cache[i].dev == dev) return (int)std::min<long>(ntiles, cache[i].cap);
   int cus = 0, per = 0;
   hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, block, 0);
+  hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, 256, 0);
   const int cap = std::max(8, cus * std::max(per, 1));
   if (used < 16) cache[used++] = Entry{(const void*)kernel, dev, cap};
   return (int)std::min<long>(ntiles, cap);
 }
 
-#ifndef TMVS_C16_NWV
-#define TMVS_C16_NWV 4
-#endif
 template <int TD, int TH>
 static int launch_conv_c16(const float* x, const float* w, const float* al, const float* sh, float* y, int B,
                            const Geo& g, hipStream_t st) {
-  constexpr int NWV = TMVS_C16_NWV;
   const long ntiles = (long)B * ((g.Do + TD - 1) / TD) * ((g.Ho + TH - 1) / TH) * ((g.Wo + 15) / 16);
-  const int grid = persistent_grid(conv3d_c16_kernel<TD, TH, NWV>, ntiles, NWV * 64);
-  hipLaunchKernelGGL((conv3d_c16_kernel<TD, TH, NWV>), dim3(grid), dim3(NWV * 64), 0, st, x, w, al, sh, y, g,
-                     (int)ntiles);
+  const int grid = persistent_grid(conv3d_c16_kernel<TD, TH>, ntiles);
+  hipLaunchKernelGGL((conv3d_c16_kernel<TD, TH>), dim3(grid), dim3(256), 0, st, x, w, al, sh, y, g, (int)ntiles);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }
@@ -1273,13 +979,13 @@ static int launch_conv_c16(const float* x, const float* w, const float* al, cons
 // taps are taken in pairs (a, b): lanes kgrp 0/1 read channel quads 0/1 of tap a, lanes 2/3
 // of tap b, one 16-byte read each; MFMA j contracts k = (tap, quad) over channel j of each
 // quad, and the A fragments are laid out to match (the 14th pair is half empty).
-template <int TD, int TH, int NWV = 4>
-__global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV == 8 ? 4 : 1))) void conv3d_s2c8_tile_kernel(const float* __restrict__ x,
+template <int TD, int TH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void conv3d_s2c8_tile_kernel(const float* __restrict__ x,
                                                                const float* __restrict__ wpk,
                                                                const float* __restrict__ alpha,
                                                                const float* __restrict__ shift, float* __restrict__ y,
                                                                Geo g, int ntiles) {
-  constexpr int CIN = 8, COUT = 16, NBW = TD * TH / NWV, NTH = NWV * 64;
+  constexpr int CIN = 8, COUT = 16, NWV = 4, NBW = TD * TH / NWV, NTH = NWV * 64;  // 4 waves per workgroup
   static_assert(TD * TH % NWV == 0, "rows split evenly over the waves");
   // (SW = 20, which offsets the staging writes' odd-column voxels by 32 banks, measured the same: r16g)
   constexpr int LW = 33, LH = 2 * TH + 1, LD = 2 * TD + 1, SW = 17;
@@ -1398,60 +1104,31 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
   }
 }
 
-#ifndef TMVS_S2C8_NWV
-#define TMVS_S2C8_NWV 4
-#endif
 template <int TD, int TH>
 static int launch_conv_s2c8_tile(const float* x, const float* w, const float* al, const float* sh, float* y, int B,
                                  const Geo& g, hipStream_t st) {
   const long ntiles = (long)B * ((g.Do + TD - 1) / TD) * ((g.Ho + TH - 1) / TH) * ((g.Wo + 15) / 16);
-  constexpr int NWV = TMVS_S2C8_NWV;
-  const int grid = persistent_grid(conv3d_s2c8_tile_kernel<TD, TH, NWV>, ntiles, NWV * 64);
-  hipLaunchKernelGGL((conv3d_s2c8_tile_kernel<TD, TH, NWV>), dim3(grid), dim3(NWV * 64), 0, st, x, w, al, sh, y, g,
-                     (int)ntiles);
+  const int grid = persistent_grid(conv3d_s2c8_tile_kernel<TD, TH>, ntiles);
+  hipLaunchKernelGGL((conv3d_s2c8_tile_kernel<TD, TH>), dim3(grid), dim3(256), 0, st, x, w, al, sh, y, g, (int)ntiles);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }
 
 // ---------------------------------------------------------------- launchers
-#ifndef TMVS_KDSKIP_MAX_DO
-#define TMVS_KDSKIP_MAX_DO 2
-#endif
-template <int CIN, int COUT, int S, int TD, int TH, int MBB, int WS = 1>
+// workgroup tile of a conv3d_lds_kernel instance: (TD, TH, MBB, WS)
+template <int TD_, int TH_, int MBB_, int WS_>
+struct LdsTile {
+  static constexpr int TD = TD_, TH = TH_, MBB = MBB_, WS = WS_;
+};
+
+// one conv3d_lds_kernel instance; the caller names the tap schedule (straight, KDSKIP or TAPOUT)
+template <int CIN, int COUT, int S, typename T, bool KDSKIP = false, bool TAPOUT = false>
 static int launch_conv(const float* x, const float* w, const float* al, const float* sh, float* y, int B,
                        const Geo& g, hipStream_t st) {
-  constexpr int MG = ((COUT + 15) / 16) / MBB;
-  const long nblk = (long)B * ((g.Do + TD - 1) / TD) * ((g.Ho + TH - 1) / TH) * ((g.Wo + 15) / 16) * MG;
-  // output depth <= 2 (the coarse levels of a D = 8 stage): every wave has a depth-padding kd slice
-  if (g.Do <= TMVS_KDSKIP_MAX_DO)
-    hipLaunchKernelGGL((conv3d_lds_kernel<CIN, COUT, S, TD, TH, MBB, WS, true>), dim3((unsigned)nblk), dim3(256), 0, st,
-                       x, w, al, sh, y, g);
-  else
-    hipLaunchKernelGGL((conv3d_lds_kernel<CIN, COUT, S, TD, TH, MBB, WS>), dim3((unsigned)nblk), dim3(256), 0, st, x, w,
-                       al, sh, y, g);
-  TMVS_CHECK_LAUNCH();
-  return TMVS_OK;
-}
-
-template <int CIN, int COUT, int S, int TD, int TH, int MBB, int WS>
-static int launch_conv_tapout(const float* x, const float* w, const float* al, const float* sh, float* y, int B,
-                              const Geo& g, hipStream_t st) {
-  constexpr int MG = ((COUT + 15) / 16) / MBB;
-  const long nblk = (long)B * ((g.Do + TD - 1) / TD) * ((g.Ho + TH - 1) / TH) * ((g.Wo + 15) / 16) * MG;
-  hipLaunchKernelGGL((conv3d_lds_kernel<CIN, COUT, S, TD, TH, MBB, WS, false, true>), dim3((unsigned)nblk), dim3(256), 0,
-                     st, x, w, al, sh, y, g);
-  TMVS_CHECK_LAUNCH();
-  return TMVS_OK;
-}
-
-template <int CIN, int COUT, int S, int NBW, int MBW>
-static int launch_conv_direct(const float* x, const float* w, const float* al, const float* sh, float* y, int B,
-                              const Geo& g, hipStream_t st) {
-  constexpr int MG = ((COUT + 15) / 16) / MBW;
-  const long n_tasks = (long)B * g.Do * ((g.Ho + NBW - 1) / NBW) * ((g.Wo + 15) / 16) * MG;
-  const int nblk = (int)((n_tasks + 3) / 4);
-  hipLaunchKernelGGL((conv3d_direct_kernel<CIN, COUT, S, NBW, MBW>), dim3(nblk), dim3(256), 0, st, x, w, al, sh, y, g,
-                     (int)n_tasks);
+  constexpr int MG = ((COUT + 15) / 16) / T::MBB;
+  const long nblk = (long)B * ((g.Do + T::TD - 1) / T::TD) * ((g.Ho + T::TH - 1) / T::TH) * ((g.Wo + 15) / 16) * MG;
+  hipLaunchKernelGGL((conv3d_lds_kernel<CIN, COUT, S, T::TD, T::TH, T::MBB, T::WS, KDSKIP, TAPOUT>),
+                     dim3((unsigned)nblk), dim3(256), 0, st, x, w, al, sh, y, g);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }
@@ -1676,78 +1353,34 @@ static int conv_dispatch(const float* x, int B, int cin, int d, int h, int w, co
   }
   // the MFMA kernels address one sample's input through a buffer with 32-bit byte offsets
   if ((long long)d * h * w * cin * 4 >= (1LL << 31)) return TMVS_ERR_SHAPE;
-  // stride 1: LDS-staged tiles, one output depth slice x 8 rows x 16 columns per workgroup
-#define TMVS_CONV_LDS(CI, CO, ...)                                                              \
-  if (cin == CI && cout == CO && stride == 1) {                                               \
-    return launch_conv<CI, CO, 1, __VA_ARGS__>(x, wpk, al, sh, y, B, g, st);                 \
+  // output depth <= 2 (the coarse levels of a D = 8 stage): every wave has a kd slice that lies wholly in
+  // the depth padding, which the KDSKIP instances do not run
+  constexpr int kKdSkipMaxDo = 2;
+  const bool kdskip = g.Do <= kKdSkipMaxDo;
+  constexpr bool KD = true, TAPOUT = true;
+  using Conv3Tile = LdsTile<2, 2, 2, 2>;    // 50.4 -> 46.0 us at stage 3 (r17n)
+  using Conv4Tile = LdsTile<2, 2, 2, 2>;    // output depth > 2 (r17h)
+  using Conv4TileKd = LdsTile<2, 4, 2, 1>;  // output depth <= 2
+  using Conv5Tile = LdsTile<1, 2, 4, 4>;    // each wave one output block: 30.4 / 15.5 / 19.1 us at stages 2 / 1 / 3 (r17j)
+  using Conv6Tile = LdsTile<1, 2, 4, 4>;    // each wave one output block (r17g)
+  int (*launch)(const float*, const float*, const float*, const float*, float*, int, const Geo&, hipStream_t) = nullptr;
+  if (stride == 1) {
+    if (cin == 16 && cout == 16)  // conv2: persistent, weights in LDS, 2x4x16-voxel tiles
+      launch = launch_conv_c16<2, 4>;
+    else if (cin == 32 && cout == 32)  // conv4
+      launch = kdskip ? launch_conv<32, 32, 1, Conv4TileKd, KD> : launch_conv<32, 32, 1, Conv4Tile>;
+    else if (cin == 64 && cout == 64)  // conv6
+      launch = kdskip ? launch_conv<64, 64, 1, Conv6Tile, KD> : launch_conv<64, 64, 1, Conv6Tile>;
+  } else {
+    // conv1's 2x2 tiles: 3 workgroups per CU (41.5 KB LDS); 2x4 measured 103 vs 97-98 us (r12e)
+    if (cin == 8 && cout == 16)  // conv1: persistent, weights in LDS, tap pairs
+      launch = launch_conv_s2c8_tile<2, 2>;
+    else if (cin == 16 && cout == 32)  // conv3
+      launch = kdskip ? launch_conv<16, 32, 2, Conv3Tile, KD> : launch_conv<16, 32, 2, Conv3Tile>;
+    else if (cin == 32 && cout == 64)  // conv5: taps outer, the K order the oracle-parity tests pin
+      launch = launch_conv<32, 64, 2, Conv5Tile, false, TAPOUT>;
   }
-#ifndef TMVS_C16_TD
-#define TMVS_C16_TD 2
-#define TMVS_C16_TH 4
-#endif
-#ifdef TMVS_C16_LDS  // A/B: conv2 through the general LDS kernel (weights from L2) with this (TD, TH, MBB, WS)
-  TMVS_CONV_LDS(16, 16, TMVS_C16_LDS)
-#endif
-  if (cin == 16 && cout == 16 && stride == 1)
-    return launch_conv_c16<TMVS_C16_TD, TMVS_C16_TH>(x, wpk, al, sh, y, B, g, st);
-#ifndef TMVS_C4_CFG
-#define TMVS_C4_CFG 2, 2, 2, 2     // (TD, TH, MBB, WS) of conv4 (32 -> 32); output depth > 2 (r17h)
-#endif
-#ifndef TMVS_C4_CFG_KD
-#define TMVS_C4_CFG_KD 2, 4, 2, 1  // output depth <= 2 (the depth-padding-skipping instance)
-#endif
-  if (cin == 32 && cout == 32 && stride == 1 && g.Do <= TMVS_KDSKIP_MAX_DO)
-    return launch_conv<32, 32, 1, TMVS_C4_CFG_KD>(x, wpk, al, sh, y, B, g, st);
-#ifndef TMVS_C6_CFG
-#define TMVS_C6_CFG 1, 2, 4, 4  // and of conv6 (64 -> 64): each wave one output block (r17g)
-#endif
-#ifndef TMVS_C3_CFG
-#define TMVS_C3_CFG 2, 2, 2, 2  // and of conv3 (16 -> 32, stride 2): 50.4 -> 46.0 us at stage 3 (r17n)
-#endif
-  TMVS_CONV_LDS(32, 32, TMVS_C4_CFG)
-  TMVS_CONV_LDS(64, 64, TMVS_C6_CFG)
-#undef TMVS_CONV_LDS
-  // stride 2, 8 -> 16 (full-resolution input): tap pairs, 16-byte loads
-#ifndef TMVS_S2C8_TD
-#define TMVS_S2C8_TD 2  // 2x2 tiles: 3 workgroups per CU (41.5 KB LDS); 2x4 measured 103 vs 97-98 us (r12e)
-#define TMVS_S2C8_TH 2
-#endif
-  if (cin == 8 && cout == 16 && stride == 2)
-    return launch_conv_s2c8_tile<TMVS_S2C8_TD, TMVS_S2C8_TH>(x, wpk, al, sh, y, B, g, st);
-#ifndef TMVS_S2_LDS
-#define TMVS_S2_LDS 1
-#endif
-#if TMVS_S2_LDS
-  // conv3 (16 -> 32, stride 2, one 16-channel chunk): the LDS-staged kernel -- each input voxel is
-  // fetched once per tile instead of once per tap that reads it (the direct form's stride-2 lane
-  // pattern half-fills every cache line it touches); same accumulation order as the direct kernel.
-  // 63.8 -> 54.2 us per stage-2/3 call (r12k). (conv5 through the LDS kernel measured no faster
-  // before the wave split, 58.0 vs 56.9 us, r12k; with it, below, it is.)
-  if (cin == 16 && cout == 32 && stride == 2) return launch_conv<16, 32, 2, TMVS_C3_CFG>(x, wpk, al, sh, y, B, g, st);
-#endif
-  // stride 2: direct
-#define TMVS_CONV_DIRECT(CI, CO, NBW, MBW) \
-  if (cin == CI && cout == CO && stride == 2) return launch_conv_direct<CI, CO, 2, NBW, MBW>(x, wpk, al, sh, y, B, g, st);
-  TMVS_CONV_DIRECT(8, 16, 4, 1)
-  TMVS_CONV_DIRECT(16, 32, 4, 1)
-#ifndef TMVS_C5_LDS
-#define TMVS_C5_LDS 1, 2, 4, 4  // conv5 (32 -> 64, stride 2) through the LDS-tiled kernel, (TD, TH, MBB, WS)
-#endif
-  // conv5 through the wave-split LDS kernel: 52.6 -> 30.4 / 24.0 -> 15.5 / 24.2 -> 19.1 us (stages 2 / 1 / 3)
-  // against the direct kernel's best tilings (2 rows x 2 blocks per wave on the stage-2/3 grids, 2 x 1 on
-  // stage 1; r12r, r12s, r17j). TMVS_C5_MODE 2 (default): both 16-channel chunks staged, taps outer -- the
-  // direct kernel's K order, so its sums bit for bit (round 6); 1: chunk-outer (round 5: re-associated
-  // sums, one stage-2 near-tie flip at C2 cascading into 23 stage-3 pixels); 0: the direct kernel.
-#ifndef TMVS_C5_MODE
-#define TMVS_C5_MODE 2
-#endif
-  if (cin == 32 && cout == 64 && stride == 2) {
-    if constexpr (TMVS_C5_MODE == 2) return launch_conv_tapout<32, 64, 2, TMVS_C5_LDS>(x, wpk, al, sh, y, B, g, st);
-    if constexpr (TMVS_C5_MODE == 1) return launch_conv<32, 64, 2, TMVS_C5_LDS>(x, wpk, al, sh, y, B, g, st);
-  }
-  TMVS_CONV_DIRECT(32, 64, 2, 1)
-#undef TMVS_CONV_DIRECT
-  return TMVS_ERR_SHAPE;
+  return launch ? launch(x, wpk, al, sh, y, B, g, st) : TMVS_ERR_SHAPE;
 }
 
 static int deconv_dispatch(const float* x, int B, int cin, int d, int h, int w, const float* wpk, const float* al,
@@ -1760,24 +1393,19 @@ static int deconv_dispatch(const float* x, int B, int cin, int d, int h, int w, 
   g.Do = 2 * d;
   g.Ho = 2 * h;
   g.Wo = 2 * w;
-#ifndef TMVS_DECONV_EVEN
-#define TMVS_DECONV_EVEN 2, 2  // (TDI, THI) input tile for an even input depth
-#define TMVS_DECONV_ODD 1, 4   // and for an odd one
-#endif
-#define TMVS_DECONV_CASE(CI, CO, MBB)                                                                       \
-  if (cin == CI && cout == CO) {                                                                           \
-    if (g.Di % 2 == 0) return launch_deconv<CI, CO, TMVS_DECONV_EVEN, MBB>(x, wpk, al, sh, skip, y, B, g, st); \
-    return launch_deconv<CI, CO, TMVS_DECONV_ODD, MBB>(x, wpk, al, sh, skip, y, B, g, st);                  \
-  }
-  TMVS_DECONV_CASE(64, 32, 1)
-  TMVS_DECONV_CASE(32, 16, 1)
-  if (cin == 16 && cout == 8) {  // W-parity outputs packed into the 16 MFMA rows
-    if (g.Di % 2 == 0) return launch_deconv_c8<2, 2>(x, wpk, al, sh, skip, y, B, g, st);
-    return launch_deconv_c8<1, 4>(x, wpk, al, sh, skip, y, B, g, st);
-  }
-#undef TMVS_DECONV_CASE
-  return TMVS_ERR_SHAPE;
+  // (TDI, THI) input tile: 2 x 2 for an even input depth, 1 x 4 for an odd one
+  const bool even = g.Di % 2 == 0;
+  int (*launch)(const float*, const float*, const float*, const float*, const float*, float*, int, const Geo&,
+                hipStream_t) = nullptr;
+  if (cin == 64 && cout == 32)
+    launch = even ? launch_deconv<64, 32, 2, 2, 1> : launch_deconv<64, 32, 1, 4, 1>;
+  else if (cin == 32 && cout == 16)
+    launch = even ? launch_deconv<32, 16, 2, 2, 1> : launch_deconv<32, 16, 1, 4, 1>;
+  else if (cin == 16 && cout == 8)  // W-parity outputs packed into the 16 MFMA rows
+    launch = even ? launch_deconv_c8<2, 2> : launch_deconv_c8<1, 4>;
+  return launch ? launch(x, wpk, al, sh, skip, y, B, g, st) : TMVS_ERR_SHAPE;
 }
+
 
 }  // namespace tmvs
 
@@ -1799,20 +1427,12 @@ extern "C" int tmvs_deconv3d_bn_relu_add(const float* x, int batch, int cin, int
   return deconv_dispatch(x, batch, cin, d, h, w, wpk, alpha, shift, cout, skip, y, (hipStream_t)stream);
 }
 
-static dim3 prob_grid(int batch, int D, int H, int W, int dchunk) {
-  return dim3((unsigned)(((W + kProbCols - 1) / kProbCols) * ((H + 3) / 4) * batch * ((D + dchunk - 1) / dchunk)));
-}
-
-// prob (8 -> 1) raw logits: one row per wave (prob_kernel) or TMVS_PROB_ROWS rows per wave
+// prob (8 -> 1) raw logits: one row per wave (two measured 42.3 -> 44.9 us at stage 1's D = 48, r16c)
 static int launch_prob(const float* x, float* y, int batch, int D, int H, int W, const float* wt, hipStream_t st) {
-  if constexpr (TMVS_PROB_ROWS > 1) {
-    constexpr int NR = TMVS_PROB_ROWS;
-    const dim3 grid((unsigned)(((W + kProbCols - 1) / kProbCols) * ((H + 4 * NR - 1) / (4 * NR)) * batch *
-                               ((D + kDChunk - 1) / kDChunk)));
-    hipLaunchKernelGGL(prob_rows_kernel<NR>, grid, dim3(256), 0, st, x, y, D, H, W, wt);
-  } else {
-    hipLaunchKernelGGL(prob_kernel, prob_grid(batch, D, H, W, kDChunk), dim3(256), 0, st, x, y, D, H, W, wt);
-  }
+  constexpr int NR = 1;
+  const dim3 grid((unsigned)(((W + kProbCols - 1) / kProbCols) * ((H + 4 * NR - 1) / (4 * NR)) * batch *
+                             ((D + kDChunk - 1) / kDChunk)));
+  hipLaunchKernelGGL(prob_kernel<NR>, grid, dim3(256), 0, st, x, y, D, H, W, wt);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }
@@ -1973,27 +1593,22 @@ extern "C" int tmvs_costregnet_wta(const float* x, const float* hyp, int batch, 
     return tmvs_softmax_wta(c0, hyp, batch, depth, height, width, clamp_lo, clamp_hi, prob, depth_out, depth_raw,
                             conf, stream);
   }
-  // D <= 32: one workgroup per (sample, row, 62-column segment), its D/8 waves prob_kernel's depth
-  // chunks. Measured (r07d vs r07b): D = 32 114.0 vs 108.4 + 15.7 us, D = 8 104.3 vs 90.9 + 18.6 us
-  constexpr int NR = TMVS_PROB_WTA_ROWS;
-  const dim3 gf((unsigned)(((width + kProbCols - 1) / kProbCols) * ((height + NR - 1) / NR) * batch));
+  // D <= 32: one workgroup per (sample, row pair, 62-column segment), its D/8 waves prob_kernel's depth
+  // chunks. Measured (r07d vs r07b): D = 32 114.0 vs 108.4 + 15.7 us, D = 8 104.3 vs 90.9 + 18.6 us;
+  // two rows per wave: the raw walk's two-row form measured 96.0 -> 92.1 / 90.9 -> 87.8 us at stages 2 / 3 (r16c)
+  constexpr int kProbWtaRows = 2;
+  const dim3 gf((unsigned)(((width + kProbCols - 1) / kProbCols) * ((height + kProbWtaRows - 1) / kProbWtaRows) * batch));
   const dim3 bf((unsigned)(64 * (depth / kDChunk)));
-#define TMVS_PW_CASE(DD)                                                                                      \
-  case DD:                                                                                                    \
-    if constexpr (NR > 1)                                                                                     \
-      hipLaunchKernelGGL((prob_wta_rows_kernel<DD, NR>), gf, bf, 0, st, x11, w->w[10], hyp, height, width,    \
-                         clamp_lo, clamp_hi, prob, depth_out, depth_raw, conf);                               \
-    else                                                                                                      \
-      hipLaunchKernelGGL(prob_wta_kernel<DD>, gf, bf, 0, st, x11, w->w[10], hyp, height, width, clamp_lo,     \
-                         clamp_hi, prob, depth_out, depth_raw, conf);                                         \
-    break;
+  auto fused = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, gf, bf, 0, st, x11, w->w[10], hyp, height, width, clamp_lo, clamp_hi, prob, depth_out,
+                       depth_raw, conf);
+  };
   switch (depth) {
-    TMVS_PW_CASE(8)
-    TMVS_PW_CASE(16)
-    TMVS_PW_CASE(24)
-    TMVS_PW_CASE(32)
+    case 8: fused(prob_wta_rows_kernel<8, kProbWtaRows>); break;
+    case 16: fused(prob_wta_rows_kernel<16, kProbWtaRows>); break;
+    case 24: fused(prob_wta_rows_kernel<24, kProbWtaRows>); break;
+    case 32: fused(prob_wta_rows_kernel<32, kProbWtaRows>); break;
   }
-#undef TMVS_PW_CASE
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }

@@ -368,9 +368,6 @@ __global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_small_kernel(
 // `direct` row once per kd and the 9 neighbours' `gathered` rows (L1/L2 hits), keeping 9 x A x BC fp32
 // sums over its voxels; then per value a fixed wave butterfly (fp64) and the 4 waves in order.
 // Replaces 27 passes over `direct` with 3.
-#ifndef TMVS_TAPS_DPP
-#define TMVS_TAPS_DPP 1
-#endif
 template <int A, int BC>
 __global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_taps_kernel(
     const float* __restrict__ direct, const float* __restrict__ gath, int B, int Pd, int Ph, int Pw, int Gd, int Gh,
@@ -454,13 +451,7 @@ __global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_taps_kernel(
   for (int k = 0; k < 9; ++k)
 #pragma unroll
     for (int q = 0; q < NPR; ++q) {
-      double x = (double)acc[k][q];
-      if (TMVS_TAPS_DPP) {
-        x = wave_xor_sum_dpp(x);  // the same butterfly (common.h)
-      } else {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-      }
+      const double x = wave_xor_sum_dpp((double)acc[k][q]);  // the fixed xor butterfly (common.h)
       if (lane == 0) red[k * NPR + q][wv] = x;
     }
   __syncthreads();
@@ -805,9 +796,6 @@ __global__ __launch_bounds__(kTrainBlock) void bn_relu_bwd_apply4_kernel(
 }
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-#ifndef TMVS_BN_VEC4
-#define TMVS_BN_VEC4 1
-#endif
 
 // ---------------------------------------------------------------- dispatch helpers
 template <int CIN, int COB>
@@ -964,7 +952,7 @@ extern "C" int tmvs_bn_relu_train_grouped(const float* z, int groups, long nvox,
   if (!z || !mean || !var || !gamma || !beta || !out || nvox <= 0 || channels <= 0 || groups <= 0)
     return TMVS_ERR_ARG;
   const long per = nvox * channels, n = per * groups;
-  if (TMVS_BN_VEC4 && channels % 4 == 0 && aligned16(z) && aligned16(out) && (!skip || aligned16(skip))) {
+  if (channels % 4 == 0 && aligned16(z) && aligned16(out) && (!skip || aligned16(skip))) {
     const long n4 = n / 4;
     hipLaunchKernelGGL(bn_relu_apply4_kernel, dim3((unsigned)((n4 + kTrainBlock - 1) / kTrainBlock)), dim3(kTrainBlock),
                        0, (hipStream_t)stream, (const float4*)z, n4, per, channels, mean, var, gamma, beta, eps,
@@ -1004,7 +992,7 @@ extern "C" int tmvs_bn_relu_backward_grouped(const float* dy, const float* z, in
                      (const double*)part, nblk, 2 * channels, sums);
   TMVS_CHECK_LAUNCH();
   const long n = nvox * channels * groups;
-  if (TMVS_BN_VEC4 && channels % 4 == 0 && aligned16(dy) && aligned16(z) && aligned16(dz)) {
+  if (channels % 4 == 0 && aligned16(dy) && aligned16(z) && aligned16(dz)) {
     const long n4 = n / 4;
     hipLaunchKernelGGL(bn_relu_bwd_apply4_kernel, dim3((unsigned)((n4 + kTrainBlock - 1) / kTrainBlock)),
                        dim3(kTrainBlock), 0, st, (const float4*)dy, (const float4*)z, n4, channels, nvox, mean, var,

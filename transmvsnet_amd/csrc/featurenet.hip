@@ -54,21 +54,6 @@ typedef float float2_t __attribute__((ext_vector_type(2)));
 // Window slot of chunk c of window pixel P.
 __device__ __forceinline__ int dcn_slot(int P, int c) { return P * 8 + (c ^ (P & 7)); }
 
-// Timing ablations (wrong outputs by construction; A/B builds only): bit 1 drops the offset-conv MFMAs,
-// 2 the bilinear blend (a tap's B operand is its first corner), 4 the tap MFMAs, 8 the window stores.
-#ifndef TMVS_DCN_ABL
-#define TMVS_DCN_ABL 0
-#endif
-#ifndef TMVS_DCN_OB12
-#define TMVS_DCN_OB12 1  // offset-conv fragment buffers at 12 waves (A/B: 2 = read one tap ahead)
-#endif
-#ifndef TMVS_DCN_SB12
-#define TMVS_DCN_SB12 1  // single tap buffers at 12 waves (A/B: 0 = double)
-#endif
-#ifndef TMVS_DCN_PK
-#define TMVS_DCN_PK 1  // the bilinear blend on packed fp32 (A/B: 0 = scalar)
-#endif
-
 // The 9 taps of one wave-unit: gather (window LDS; beyond it, global, unless FAST), blend,
 // modulate, MT x 8 MFMAs per tap.
 // SB: one gather / A-fragment buffer (a tap's blend consumes the gathers before the next tap's refill
@@ -132,22 +117,6 @@ __device__ __forceinline__ void dcn_taps(floatx4_t (&acc)[MT], const floatx4_t* 
     // per element as the scalar form, half the VALU issue)
 #pragma unroll
     for (int e = 0; e < 8; e += 2) {
-      if (TMVS_DCN_ABL & 2) {
-        b[e] = v[bb][0][e >> 2][e & 3];
-        b[e + 1] = v[bb][0][e >> 2][(e & 3) + 1];
-        continue;
-      }
-      if (!TMVS_DCN_PK) {
-#pragma unroll
-        for (int f = e; f < e + 2; ++f) {
-          float val = w4[bb][0] * v[bb][0][f >> 2][f & 3];
-          val = val + w4[bb][1] * v[bb][1][f >> 2][f & 3];
-          val = val + w4[bb][2] * v[bb][2][f >> 2][f & 3];
-          val = val + w4[bb][3] * v[bb][3][f >> 2][f & 3];
-          b[f] = mk[bb] * val;
-        }
-        continue;
-      }
       auto pr = [&](int c) { return float2_t{v[bb][c][e >> 2][e & 3], v[bb][c][e >> 2][(e & 3) + 1]}; };
       auto bc = [](float t) { return float2_t{t, t}; };
       float2_t val = bc(w4[bb][0]) * pr(0);
@@ -164,10 +133,6 @@ __device__ __forceinline__ void dcn_taps(floatx4_t (&acc)[MT], const floatx4_t* 
     for (int s = 0; s < 8; ++s)
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
-        if (TMVS_DCN_ABL & 4) {
-          acc[m][0] += b[s];
-          continue;
-        }
         if (MT == 1 && (s & 1))  // one output tile: two interleaved chains hide the dependent latency
           alt = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m][s >> 2][s & 3], b[s], alt, 0, 0, 0);
         else
@@ -343,8 +308,7 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
 #pragma unroll
     for (int i = 0; i < Cfg::STAGE; ++i) {
       const int idx = tid + NT * i;
-      if ((Cfg::WIN4 % NT == 0 || idx < Cfg::WIN4) && (!(TMVS_DCN_ABL & 8) || u == u_begin))
-        win[dcn_slot(idx >> 3, idx & 7)] = stg[i];
+      if (Cfg::WIN4 % NT == 0 || idx < Cfg::WIN4) win[dcn_slot(idx >> 3, idx & 7)] = stg[i];
     }
     __syncthreads();
     if (u + 1 < u_end) fetch(u + 1);  // next window in flight during this unit's work
@@ -356,7 +320,7 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
       // window pixel (wv + HALO + ki - 1, HALO + n + kj - 1); D lane (j, n) = channels 16m + 4j + i
       // (tap k + 1's fragments are read during tap k's MFMAs)
       floatx4_t ao[2] = {floatx4_t{0.f, 0.f, 0.f, 0.f}, floatx4_t{0.f, 0.f, 0.f, 0.f}};
-      constexpr int OB = NW > 8 ? TMVS_DCN_OB12 : 2;  // 3 waves/SIMD: read each tap's fragments just before it
+      constexpr int OB = NW > 8 ? 1 : 2;  // 3 waves/SIMD: one buffer, each tap's fragments read just before it
       floatx4_t fb[OB][2], fa[OB][2][2];
       auto frag = [&](int k, int bf) {
         const int ki = k / 3, kj = k - 3 * ki;
@@ -383,14 +347,9 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
 #pragma unroll
         for (int s = 0; s < 8; ++s)
 #pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            if (TMVS_DCN_ABL & 1) {
-              ao[m][0] += (s < 4 ? b0[s] : b1[s - 4]) * a[m][s >> 2][s & 3];
-              continue;
-            }
+          for (int m = 0; m < 2; ++m)
             ao[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m][s >> 2][s & 3], s < 4 ? b0[s] : b1[s - 4], ao[m], 0,
                                                          0, 0);
-          }
       }
       // [px][33] tile (odd row stride: the record builders' column reads hit 16 distinct banks),
       // consumed before the records overwrite it
@@ -452,7 +411,7 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
     floatx4_t acc[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = floatx4_t{0.f, 0.f, 0.f, 0.f};
-    constexpr bool SB = NW > 8 && TMVS_DCN_SB12;  // 3 waves/SIMD: single buffers
+    constexpr bool SB = NW > 8;  // 3 waves/SIMD: single buffers
     if (fast)
       dcn_taps<MT, true, Cfg::WC, SB>(acc, wl, win, recs[wv], rx, H, W, lane);
     else if (SB)
@@ -682,18 +641,13 @@ extern "C" int tmvs_deform_conv2d_pack(const float* weight, int cout, int cin, f
 
 namespace {
 
-// The DCN unit: TMVS_DCN_NW waves (rows) per workgroup with a TMVS_DCN_HALO-pixel window margin
-#ifndef TMVS_DCN_NW
-#define TMVS_DCN_NW 12
-#endif
-#ifndef TMVS_DCN_HALO
-#define TMVS_DCN_HALO 3
-#endif
+// The DCN unit: kDcnWaves waves (rows) per workgroup with a kDcnHalo-pixel window margin
+constexpr int kDcnWaves = 12, kDcnHalo = 3;
 template <int CO, bool FUSED>
 int dcn_launch(const float* x, const float* om, const float* wom, const float* bom, const float* w,
                const float* bias, const float* alpha, const float* shift, int relu, int batch, int height, int width,
                float* out, float* out_nhwc, hipStream_t st, float* om_out = nullptr) {
-  constexpr int NW = TMVS_DCN_NW, HL = TMVS_DCN_HALO;
+  constexpr int NW = kDcnWaves, HL = kDcnHalo;
   // persistent grid: one block per CU slot the kernel's LDS/VGPR footprint allows
   static int grid = 0;
   if (!grid) {

@@ -228,9 +228,6 @@ __global__ __launch_bounds__(kBlk) void conv2d_wgrad_kernel(const float* __restr
   tile_reduce_any<AP, BC>(v0, v1, la, lb, partial + ((size_t)rb * K * K + k) * AP * BC);
 }
 
-#ifndef TMVS_SMALL_DPP
-#define TMVS_SMALL_DPP 1
-#endif
 // few channels on the gathered side (the image: 3): thread t owns pairs t, t+256, .. of a x b,
 // straight from global memory (L1 hits), fp32 over a block's pixels in 8 interleaved chains, fp64 after
 template <int A, int BC>
@@ -268,13 +265,7 @@ __global__ __launch_bounds__(kBlk) void conv2d_wgrad_small_kernel(const float* _
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int q = 0; q < NPR; ++q) {
-    double x = (double)acc[q];
-    if (TMVS_SMALL_DPP) {
-      x = wave_xor_sum_dpp(x);  // the same butterfly (common.h)
-    } else {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    }
+    const double x = wave_xor_sum_dpp((double)acc[q]);  // the fixed xor butterfly (common.h)
     if (lane == 0) red[q][wv] = x;
   }
   __syncthreads();
@@ -435,25 +426,19 @@ __device__ __forceinline__ int dcn_fix_shift(const unsigned* __restrict__ mx, in
 // written whole to scratch [block][cell][32] (plain, coalesced stores); dcn_gather_windows_kernel then
 // sums, for every texel, the <= 4 windows covering it in a fixed block order (no global atomics).
 // Corners beyond the window (offsets over R px) are added to dx with fp32 atomics before that pass.
-// dcol on the matrix cores (TMVS_DCNB_MFMA, the 32-output-channel instance): per pass and tap pair,
+// dcol on the matrix cores (kMf, the 32-output-channel instance): per pass and tap pair,
 // each wave computes the 16 x 64 tile D[(tap, channel)][pixel] = sum_o W[o][channel][tap] dy[pixel][o]
 // as v_mfma_f32_16x16x4f32 chains over o (the same fmaf chain, bitwise, as the VALU form's
 // dc[c] = fmaf(g[o], w[o][c], dc[c]), o ascending), parks it in a wave-private LDS tile, and every lane
 // reads its pixel's 8 channels back, so the 9216 dcol MACs per pixel run beside the VALU's sampling,
 // offset gradients and scatter (r14w: 2163 -> 2066 / 622 -> 559 / 200 -> 158 us at 4 x 576x768 /
 // 288x384 / 144x192; the 8- and 16-channel instances measured slower that way and keep the VALU form).
-#ifndef TMVS_DCNB_MFMA
-#define TMVS_DCNB_MFMA 1
-#endif
-// The scatter's fixed-point conversion in fp32 (TMVS_DCNB_FIX32): ldexpf(f * dcol, k) is exact (a power-of-two
+// The scatter's fixed-point conversion in fp32: ldexpf(f * dcol, k) is exact (a power-of-two
 // scale of an fp32 value, no overflow below 2^62, and a result in the denormal range rounds to 0 either
 // way) and llrintf rounds it to nearest-even as __double2ll_rn does the fp64 value: the same integers
 // (bitwise, r14x). Faster for the VALU-dcol instances (32 -> 8: 1725 -> 1599 us), slower for the MFMA one
 // (2109 -> 2228 us, 2 VGPRs spilled; with the dy^T operands re-read per tap pair to make room, 3480 us,
 // r14z), so only there.
-#ifndef TMVS_DCNB_FIX32
-#define TMVS_DCNB_FIX32 1
-#endif
 template <int CO>
 __global__ __launch_bounds__(kBlk) __attribute__((amdgpu_waves_per_eu(CO == 8 ? 4 : 3,
                                                                      CO == 8 ? 4 : 3)))
@@ -461,7 +446,7 @@ void dcn_bwd_data_kernel(const float* __restrict__ x, const float* __restrict__ 
                          const float* __restrict__ dy, int B, int H, int W, const unsigned* __restrict__ absmax,
                          float* __restrict__ dx, float* __restrict__ dom, float* __restrict__ scratch) {
   using namespace dbw;
-  constexpr bool kMf = TMVS_DCNB_MFMA && CO == 32;
+  constexpr bool kMf = CO == 32;
   __shared__ unsigned long long win[WR * WC * CC];
   const int kfix = dcn_fix_shift(absmax, CO);
   const int tid = threadIdx.x;
@@ -612,8 +597,8 @@ void dcn_bwd_data_kernel(const float* __restrict__ x, const float* __restrict__ 
             for (int c = 0; c < CC; ++c)
               atomicAdd(wp + c * (WR * WC),
                         (unsigned long long)(kfix == kFixBad ? 0ll
-                                             : TMVS_DCNB_FIX32 && !kMf ? (long long)llrintf(ldexpf(f * dc[c], kfix))
-                                                               : __double2ll_rn(ldexp((double)(f * dc[c]), kfix))));
+                                             : !kMf ? (long long)llrintf(ldexpf(f * dc[c], kfix))
+                                                    : __double2ll_rn(ldexp((double)(f * dc[c]), kfix))));
           } else {  // an offset beyond the window: straight to global memory
             float* gp = dxb + ((size_t)cy * W + cx) * 32 + cc * CC;
             // the gather pass must read `far` (every writer stores the same 1; the word follows the two maxima)
@@ -698,9 +683,6 @@ __global__ __launch_bounds__(kBlk) void dcn_gather_windows_kernel(const float* _
 // dW[k][o][c] = sum_p dy[p][o] col_k[p][c]: grid (nblk, 9), block partials [nblk][9][CO][32]. A thread
 // stages two channel quads of one pixel (BROW), so the pixel's sample geometry (offsets, sigmoid mask,
 // bilinear weights) is derived once for both instead of once per quad.
-#ifndef TMVS_DCNW_BROW
-#define TMVS_DCNW_BROW 1
-#endif
 template <int CO>
 __global__ __launch_bounds__(kBlk) void dcn_bwd_weight_kernel(const float* __restrict__ x, const float* __restrict__ om,
                                                              const float* __restrict__ dy, int B, int H, int W, long ppb,
@@ -738,7 +720,6 @@ __global__ __launch_bounds__(kBlk) void dcn_bwd_weight_kernel(const float* __res
     const long p = (long)yy * W + xx;
     return dcn_sample(om + (size_t)b * 27 * HW + p, (size_t)HW, yy, xx, k, H, W);
   };
-#if TMVS_DCNW_BROW
   auto lb = [&](long v, int q0, float4 (&o)[2]) {
     int b;
     const DcnSample s = sample_at(v, b);
@@ -746,15 +727,7 @@ __global__ __launch_bounds__(kBlk) void dcn_bwd_weight_kernel(const float* __res
     o[0] = col_quad(s, b, q0);
     o[1] = col_quad(s, b, q0 + 1);
   };
-#else
-  auto lb = [&](long v, int q) {
-    int b;
-    const DcnSample s = sample_at(v, b);
-    if (!s.inside) return make_float4(0.f, 0.f, 0.f, 0.f);
-    return col_quad(s, b, q);
-  };
-#endif
-  tile_reduce_any<CO, 32, TMVS_DCNW_BROW>(v0, v1, la, lb, partial + ((size_t)rb * 9 + k) * CO * 32);
+  tile_reduce_any<CO, 32, true>(v0, v1, la, lb, partial + ((size_t)rb * 9 + k) * CO * 32);
 }
 
 // ---------------------------------------------------------------- small backward pieces

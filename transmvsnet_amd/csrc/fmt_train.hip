@@ -267,9 +267,6 @@ __global__ __launch_bounds__(kTB) void layer_norm_fwd_kernel(const float* __rest
 }
 
 // dx = rstd/32 * (32*gy - sum gy - xhat * sum gy*xhat), gy = dy * g; partial[blk] = {sum dy*xhat (32), sum dy (32)}
-#ifndef TMVS_LN_DPP
-#define TMVS_LN_DPP 1
-#endif
 __global__ __launch_bounds__(kTB) void layer_norm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                              long T, const float* __restrict__ g, long tpb,
                                                              float* __restrict__ dx, double* __restrict__ partial) {
@@ -319,13 +316,7 @@ __global__ __launch_bounds__(kTB) void layer_norm_bwd_kernel(const float* __rest
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < 64; ++i) {
-    double val = (double)(i < 32 ? pg[i] : pb[i - 32]);
-    if (TMVS_LN_DPP) {
-      val = wave_xor_sum_dpp(val);  // the same butterfly (common.h)
-    } else {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) val += __shfl_xor(val, off, 64);
-    }
+    const double val = wave_xor_sum_dpp((double)(i < 32 ? pg[i] : pb[i - 32]));  // the fixed xor butterfly (common.h)
     if (lane == 0) red[i][wv] = val;
   }
   __syncthreads();

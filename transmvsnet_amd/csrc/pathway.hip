@@ -22,31 +22,19 @@ struct Axis {
 // The lateral halo values (NCHW, the FeatureNet output) do not depend on the coarse reduction:
 // every thread requests its <= 2 halo pixels' CF channels before phase 1, so their HBM latency
 // overlaps the reduction instead of sitting after the first barrier. Out-of-image pixels read 0.
-#ifndef TMVS_PATHWAY_PREFETCH
-#define TMVS_PATHWAY_PREFETCH 1
-#endif
 constexpr int kHaloIters = (kHalo * kHalo + 255) / 256;
 
 // Tiles are dealt out XCD-contiguously over a 1-D grid (x fastest, then y, then view): consecutive
 // block ids go to different XCDs, so with the plain 3-D grid a tile's x/y neighbours -- which read
 // the same 128-B lines of the halo rows (an 18-float NCHW row spans 2-3 lines) -- sat behind
 // different L2s and each re-fetched them.
-#ifndef TMVS_PATHWAY_XCD
-#define TMVS_PATHWAY_XCD 1
-#endif
 __device__ __forceinline__ void pathway_tile(int W, int H, int& v, int& y0, int& x0) {
-#if TMVS_PATHWAY_XCD
   const int nbx = (W + kTile - 1) / kTile, nby = (H + kTile - 1) / kTile;
   int lb = xcd_remap(blockIdx.x, gridDim.x);
   x0 = (lb % nbx) * kTile;
   lb /= nbx;
   y0 = (lb % nby) * kTile;
   v = lb / nby;
-#else
-  v = blockIdx.z;
-  y0 = blockIdx.y * kTile;
-  x0 = blockIdx.x * kTile;
-#endif
 }
 
 template <int CF>
@@ -76,106 +64,11 @@ __device__ __forceinline__ Axis up_axis(int dst, int in_size, int out_size) {
   return a;
 }
 
-template <int CC, int CF>
-__global__ __launch_bounds__(256) void pathway_kernel(const float* __restrict__ coarse,
-                                                      const float* __restrict__ lateral, long lat_stride,
-                                                      const float* __restrict__ wred,
-                                                      const float* __restrict__ wsm, int h, int w,
-                                                      float* __restrict__ out) {
-  __shared__ float red[CF][kCoarse][kCoarse + 1];
-  __shared__ float inb[CF][kHalo][kHalo + 1];
-  const int H = 2 * h, W = 2 * w;
-  int v, y0, x0;
-  pathway_tile(W, H, v, y0, x0);
-  const int cy0 = y0 / 2 - 1, cx0 = x0 / 2 - 1;
-  const float* cv = coarse + (size_t)v * h * w * CC;
-  const float* lv = lateral + (size_t)v * lat_stride;
-#if TMVS_PATHWAY_PREFETCH
-  float lat[kHaloIters][CF];
-  load_lateral<CF>(lv, y0, x0, H, W, lat);
-#endif
-  // 1) 1x1 reduction of the coarse patch
-  for (int idx = threadIdx.x; idx < kCoarse * kCoarse; idx += blockDim.x) {
-    const int r = idx / kCoarse, c = idx - r * kCoarse;
-    const int cy = cy0 + r, cx = cx0 + c;
-    if (cy < 0 || cy >= h || cx < 0 || cx >= w) continue;
-    float xin[CC];
-    const float* p = cv + ((size_t)cy * w + cx) * CC;
-#pragma unroll
-    for (int i4 = 0; i4 < CC / 4; ++i4) {
-      const float4 t = *reinterpret_cast<const float4*>(p + 4 * i4);
-      xin[4 * i4] = t.x;
-      xin[4 * i4 + 1] = t.y;
-      xin[4 * i4 + 2] = t.z;
-      xin[4 * i4 + 3] = t.w;
-    }
-    float acc[CF];
-#pragma unroll
-    for (int o = 0; o < CF; ++o) acc[o] = 0.f;
-#pragma unroll 2
-    for (int i = 0; i < CC; ++i)
-#pragma unroll
-      for (int o = 0; o < CF; ++o) acc[o] = fmaf(wred[i * CF + o], xin[i], acc[o]);
-#pragma unroll
-    for (int o = 0; o < CF; ++o) red[o][r][c] = acc[o];
-  }
-  __syncthreads();
-  // 2) bilinear x2 up-sampling + lateral over the 18x18 halo (zero outside the image)
-#pragma unroll
-  for (int it = 0; it < kHaloIters; ++it) {
-    const int idx = threadIdx.x + 256 * it;
-    if (idx >= kHalo * kHalo) break;
-    const int r = idx / kHalo, c = idx - r * kHalo;
-    const int y = y0 - 1 + r, x = x0 - 1 + c;
-    if (y < 0 || y >= H || x < 0 || x >= W) {
-#pragma unroll
-      for (int o = 0; o < CF; ++o) inb[o][r][c] = 0.f;
-      continue;
-    }
-    const Axis ay = up_axis(y, h, H), ax = up_axis(x, w, W);
-    const int r0 = ay.i0 - cy0, r1 = ay.i1 - cy0, c0 = ax.i0 - cx0, c1 = ax.i1 - cx0;
-#pragma unroll
-    for (int o = 0; o < CF; ++o) {
-      const float t0 = fmaf(red[o][r0][c0], ax.l0, red[o][r0][c1] * ax.l1);
-      const float t1 = fmaf(red[o][r1][c0], ax.l0, red[o][r1][c1] * ax.l1);
-      const float up = fmaf(t0, ay.l0, t1 * ay.l1);
-#if TMVS_PATHWAY_PREFETCH
-      inb[o][r][c] = up + lat[it][o];
-#else
-      inb[o][r][c] = up + lv[((size_t)o * H + y) * W + x];
-#endif
-    }
-  }
-  __syncthreads();
-  // 3) 3x3 smoothing conv, one output pixel per thread
-  const int ty = threadIdx.x / kTile, tx = threadIdx.x - ty * kTile;
-  const int y = y0 + ty, x = x0 + tx;
-  if (y >= H || x >= W) return;
-  float acc[CF];
-#pragma unroll
-  for (int o = 0; o < CF; ++o) acc[o] = 0.f;
-#pragma unroll 1
-  for (int i = 0; i < CF; ++i) {
-#pragma unroll 3
-    for (int k = 0; k < 9; ++k) {
-      const float xv = inb[i][ty + k / 3][tx + k % 3];
-      const float* __restrict__ wk = wsm + (i * 9 + k) * CF;  // 16 consecutive weights: one s_load
-#pragma unroll
-      for (int o = 0; o < CF; ++o) acc[o] = fmaf(wk[o], xv, acc[o]);
-    }
-  }
-  float4* op = reinterpret_cast<float4*>(out + (((size_t)v * H + y) * W + x) * CF);
-#pragma unroll
-  for (int o4 = 0; o4 < CF / 4; ++o4) op[o4] = make_float4(acc[4 * o4], acc[4 * o4 + 1], acc[4 * o4 + 2], acc[4 * o4 + 3]);
-}
-
 // Stage-3 form with R output rows per thread: a workgroup owns a 16 x 16R tile, so the two
 // barriers, the coarse/halo staging and every scalar weight load are shared by R pixels. Tap
-// (i, k) feeds the R accumulator sets back to back; each output's chain keeps pathway_kernel's
-// (i, k, o) order, so the results are bitwise those of pathway_kernel.
-#ifndef TMVS_PW_R
-#define TMVS_PW_R 2
-#endif
+// (i, k) feeds the R accumulator sets back to back; each output's chain runs in (i, k, o) order
+// whatever R is, so the results do not depend on it.
+constexpr int kPathwayRows = 2;
 template <int CC, int CF, int R>
 __global__ __launch_bounds__(256) void pathway_rows_kernel(const float* __restrict__ coarse,
                                                            const float* __restrict__ lateral, long lat_stride,
@@ -316,11 +209,9 @@ __global__ __launch_bounds__(256) void pathway16_mfma_kernel(const float* __rest
   const int cy0 = y0 / 2 - 1, cx0 = x0 / 2 - 1;
   const float* cv = coarse + (size_t)v * h * w * CC;
   const float* lv = lateral + (size_t)v * lat_stride;
-#if TMVS_PATHWAY_PREFETCH
   float lat[kHaloIters][CF];
   load_lateral<CF>(lv, y0, x0, H, W, lat);
-#endif
-  // 1) 1x1 reduction of the coarse patch (as pathway_kernel)
+  // 1) 1x1 reduction of the coarse patch (as pathway_rows_kernel)
   for (int idx = threadIdx.x; idx < kCoarse * kCoarse; idx += blockDim.x) {
     const int r = idx / kCoarse, c = idx - r * kCoarse;
     const int cy = cy0 + r, cx = cx0 + c;
@@ -373,11 +264,7 @@ __global__ __launch_bounds__(256) void pathway16_mfma_kernel(const float* __rest
       const float t0 = fmaf(red[o][r0][c0], ax.l0, red[o][r0][c1] * ax.l1);
       const float t1 = fmaf(red[o][r1][c0], ax.l0, red[o][r1][c1] * ax.l1);
       const float up = fmaf(t0, ay.l0, t1 * ay.l1);
-#if TMVS_PATHWAY_PREFETCH
       inb[halo16_index(idx, o)] = up + lat[it][o];
-#else
-      inb[halo16_index(idx, o)] = up + lv[((size_t)o * H + y) * W + x];
-#endif
     }
   }
   __syncthreads();
@@ -418,28 +305,19 @@ extern "C" int tmvs_fmt_pathway(const float* coarse, const float* lateral, long 
                                 const float* w_reduce, const float* w_smooth, int nv, int cc, int cf, int h, int w,
                                 float* out, void* stream) {
   if (!coarse || !lateral || !w_reduce || !w_smooth || !out || nv <= 0 || h <= 0 || w <= 0) return TMVS_ERR_ARG;
-#if TMVS_PATHWAY_XCD
   const long nblk = (long)((2 * w + kTile - 1) / kTile) * ((2 * h + kTile - 1) / kTile) * nv;
   if (nblk > 0x7fffffffL) return TMVS_ERR_SHAPE;
   const dim3 grid((unsigned)nblk);
-#else
-  const dim3 grid((2 * w + kTile - 1) / kTile, (2 * h + kTile - 1) / kTile, nv);
-#endif
   hipStream_t st = (hipStream_t)stream;
   if (cc == 32 && cf == 16)
     hipLaunchKernelGGL((pathway16_mfma_kernel<32>), grid, dim3(256), 0, st, coarse, lateral, lat_view_stride,
                        w_reduce, w_smooth, h, w, out);
   else if (cc == 16 && cf == 8) {
-#if TMVS_PW_R > 1
-    const long nrb = (long)((2 * w + kTile - 1) / kTile) * ((2 * h + kTile * TMVS_PW_R - 1) / (kTile * TMVS_PW_R)) * nv;
-    hipLaunchKernelGGL((pathway_rows_kernel<16, 8, TMVS_PW_R>), dim3((unsigned)nrb), dim3(256), 0, st, coarse, lateral,
+    constexpr int R = kPathwayRows;
+    const long nrb = (long)((2 * w + kTile - 1) / kTile) * ((2 * h + kTile * R - 1) / (kTile * R)) * nv;
+    hipLaunchKernelGGL((pathway_rows_kernel<16, 8, R>), dim3((unsigned)nrb), dim3(256), 0, st, coarse, lateral,
                        lat_view_stride, w_reduce, w_smooth, h, w, out);
-#else
-    hipLaunchKernelGGL((pathway_kernel<16, 8>), grid, dim3(256), 0, st, coarse, lateral, lat_view_stride, w_reduce,
-                       w_smooth, h, w, out);
-#endif
-  }
-  else
+  } else
     return TMVS_ERR_SHAPE;
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;

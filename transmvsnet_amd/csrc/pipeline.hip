@@ -61,17 +61,13 @@ extern "C" size_t tmvs_fmt_forward_split_workspace(int nv, int l_tokens) {
          align_up256((size_t)(4 + 1 + (nv - 1)) * TMVS_KV_NFLOATS * 4);
 }
 
-#ifndef TMVS_FMT_SPLIT_ORDER
-#define TMVS_FMT_SPLIT_ORDER 0
-#endif
-#ifndef TMVS_SPLIT_REF_TPW
+namespace {
 // tiles per wave of the reference view's applies (0: occupancy-sized, as if the launch were alone). Beside the
 // source views' launches a 1-view apply of 2 tiles per wave (half the waves) measured 297.8 vs 296.6 depth maps/s
 // (4: 297.4, 8: 293.6; profiles/r22/reftpw_ab.txt); the tokens are the same either way
-#define TMVS_SPLIT_REF_TPW 2
-#endif
+constexpr int kSplitRefTilesPerWave = 2;
 
-namespace {
+
 // fork / cross-layer / join events of tmvs_fmt_forward_split, created once per host thread and device
 // (thread_local: concurrent host threads never share an event; within one thread every record is
 // followed by its waits in the same call, so a wait always binds to this call's record)
@@ -129,7 +125,7 @@ extern "C" int tmvs_fmt_forward_split(const float* stage1, long view_stride, con
     const int i = 2 * j;
     int r;
     if ((r = tmvs_fmt_kv_grouped(tokens, 1, nv, L, enc_w[i], slab_side, sd, kv_ref, ss))) return r;
-    if ((r = tmvs_fmt_apply_tiled(tokens, 1, L, kv_ref, TMVS_KV_NFLOATS, enc_w[i], TMVS_SPLIT_REF_TPW, ss))) return r;
+    if ((r = tmvs_fmt_apply_tiled(tokens, 1, L, kv_ref, TMVS_KV_NFLOATS, enc_w[i], kSplitRefTilesPerWave, ss))) return r;
     if ((r = tmvs_fmt_kv(tokens, 1, L, enc_w[i + 1], slab_side, sd, kv_cross + j * TMVS_KV_NFLOATS, ss))) return r;
     return hipEventRecord(e->ev[1 + j], ss) != hipSuccess ? TMVS_ERR_HIP : TMVS_OK;
   };
@@ -143,15 +139,11 @@ extern "C" int tmvs_fmt_forward_split(const float* stage1, long view_stride, con
     if (hipStreamWaitEvent(ms, e->ev[1 + j], 0) != hipSuccess) return TMVS_ERR_HIP;
     return tmvs_fmt_apply(src, nv - 1, L, kv_cross + j * TMVS_KV_NFLOATS, 0, enc_w[2 * j + 1], ms);
   };
-  if (TMVS_FMT_SPLIT_ORDER == 0) {  // the reference chain enqueued whole, then the source views'
-    for (int j = 0; j < 4; ++j)
-      if ((rc = ref_layer(j))) return rc;
-    for (int j = 0; j < 4; ++j)
-      if ((rc = src_self(j)) || (rc = src_cross(j))) return rc;
-  } else {  // layer by layer
-    for (int j = 0; j < 4; ++j)
-      if ((rc = src_self(j)) || (rc = ref_layer(j)) || (rc = src_cross(j))) return rc;
-  }
+  // the reference chain enqueued whole, then the source views'
+  for (int j = 0; j < 4; ++j)
+    if ((rc = ref_layer(j))) return rc;
+  for (int j = 0; j < 4; ++j)
+    if ((rc = src_self(j)) || (rc = src_cross(j))) return rc;
   if (hipEventRecord(e->ev[5], ss) != hipSuccess) return TMVS_ERR_HIP;
   if (hipStreamWaitEvent(ms, e->ev[5], 0) != hipSuccess) return TMVS_ERR_HIP;
   return TMVS_OK;

@@ -542,8 +542,8 @@ __device__ __forceinline__ float reduce_scatter(const float* p, int k) {
 }
 
 // Which samples share a load instruction. Plane-major rounds (the original layout): in round t the
-// wave's SPW groups sample SPW pixels at one plane each. Pixel-major rounds (TMVS_WARP_PMAJOR, used
-// for C = 16): the SPW groups sample PPR = SPW/LPS pixels × LPS consecutive planes each (stage 2:
+// wave's SPW groups sample SPW pixels at one plane each. Pixel-major rounds (used for C = 16): the
+// SPW groups sample PPR = SPW/LPS pixels × LPS consecutive planes each (stage 2:
 // 1 pixel × 8 planes), whose taps lie ≈0.7 px apart on one epipolar segment and so share cache lines.
 // Group g's round-t sample is owned by its lane t (geometry broadcast as before), so lane (g, k) owns
 // pixel k·PPR + g/LPS at planes j·LPS + g%LPS and holds the reference quads of the LPS pixels its
@@ -552,13 +552,6 @@ __device__ __forceinline__ float reduce_scatter(const float* p, int k) {
 // alternating reps in one box): stage 2 345.1 -> 323.3 us, stage 3 247.2 -> 252.1 us (the address
 // unit is charged per 4-lane quad, so sharing lines between quads buys little); C = 8 keeps the
 // plane-major rounds.
-#ifndef TMVS_WARP_PMAJOR
-#define TMVS_WARP_PMAJOR 1
-#endif
-#ifndef TMVS_WARP_PAD
-#define TMVS_WARP_PAD 0
-#endif
-
 template <int C, int D, bool PARTIAL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void warp_pair_kernel(
     const float* __restrict__ ref, const float* __restrict__ src, const float* __restrict__ hyp,
@@ -567,8 +560,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   constexpr int NQ = C / 4;             // channel quads
   constexpr int LPS = 2 * NQ;           // lanes per pixel: (tap column, quad)
   constexpr int SPW = 64 / LPS, PIX = 4 * SPW, DPT = D / LPS;
-  constexpr bool PM = TMVS_WARP_PMAJOR && C == 16;  // pixel-major rounds
-  constexpr int PPR = PM ? SPW / LPS : SPW;          // pixels per round
+  constexpr bool PM = C == 16;               // pixel-major rounds
+  constexpr int PPR = PM ? SPW / LPS : SPW;  // pixels per round
   static_assert(C == 8 || C == 16, "row-pair layout for 8 or 16 channels");
   static_assert(D % LPS == 0, "D must be a multiple of the lanes per pixel");
   static_assert(!PM || PPR * LPS == SPW, "pixel-major rounds: LPS^2 must divide 64");
@@ -576,10 +569,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   __shared__ float acc_lds[DPT][256];
   const int tid = threadIdx.x;
   const int HW = H * W;
-#if TMVS_WARP_PAD
-  __shared__ float pad_lds[TMVS_WARP_PAD];  // A/B only: dead LDS that caps blocks per CU
-  if (H < 0) pad_lds[tid] = 0.f;
-#endif
   const int nblk = (HW + PIX - 1) / PIX;
   const int tile = xcd_remap(blockIdx.x, nblk);
   const int lane = tid & 63;
@@ -778,13 +767,10 @@ __global__ __launch_bounds__(256) void warp_corr_bwd_kernel(const float* __restr
   unsigned skey[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
   float scoef[4] = {0.f, 0.f, 0.f, 0.f};
   unsigned long long* dv = dsrc_fix + (size_t)v * HW * C;
-  // the block's reference rows in LDS (TMVS_WARP_BWD_SREF): a flush round reads its items' rows from
-  // there, not from global memory -- one round is a chain of lane exchanges, the row read, the
-  // fixed-point conversion and the atomic, and a global read had put a memory latency into every round
-#ifndef TMVS_WARP_BWD_SREF
-#define TMVS_WARP_BWD_SREF 1
-#endif
-  constexpr bool kSref = SCATTER && TMVS_WARP_BWD_SREF;
+  // the block's reference rows in LDS: a flush round reads its items' rows from there, not from global
+  // memory -- one round is a chain of lane exchanges, the row read, the fixed-point conversion and the
+  // atomic, and a global read had put a memory latency into every round
+  constexpr bool kSref = SCATTER;
   __shared__ __attribute__((aligned(16))) float sref[kSref ? 256 * C : 4];
   if constexpr (kSref) {
     static_assert(C % 4 == 0, "float4 rows");
