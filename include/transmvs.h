@@ -575,7 +575,9 @@ int tmvs_entropy_loss(const float* prob, const float* depth_values, int dv_per_p
                       void* workspace, size_t workspace_bytes, float* out, float* wta_depth, float* photo_conf,
                       float* grad_logits, void* stream);
 /* focal_loss_bld's metrics (module.py:581-587): err = |gt - depth| / (depth_interval * 192 / 128) over
- * the n masked elements; out (device, 3 floats) = {epe, less1, less3}; NaN for an empty mask.      */
+ * the n masked elements; out (device, 3 floats) = {epe, less1, less3}; NaN for an empty mask.
+ * KNOWN MISMATCH: n <= 0 is rejected with TMVS_ERR_SHAPE, not the TMVS_ERR_ARG that the status table
+ * above gives for a non-positive size (tests/test_abi.py pins the current value).                  */
 size_t tmvs_depth_metrics_workspace(int n);
 int tmvs_depth_metrics(const float* depth, const float* depth_gt, const float* mask, int n, float depth_interval,
                        void* workspace, size_t workspace_bytes, float* out, void* stream);

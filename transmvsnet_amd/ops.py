@@ -863,6 +863,8 @@ def upsample2_backward_nhwc(du):
     """tmvs_upsample2_backward_nhwc: du [N,2h,2w,C] -> dr [N,h,w,C]."""
     _dev(du, "du")
     n, hh, ww, c = du.shape
+    if hh % 2 or ww % 2:
+        raise ValueError("upsample2_backward_nhwc: du must be [N, 2h, 2w, C]")
     dr = torch.empty(n, hh // 2, ww // 2, c, device=du.device)
     with _Span("tmvs_upsample2_backward_nhwc"):
         _lib.check(_lib_h().tmvs_upsample2_backward_nhwc(_ptr(du), n, hh // 2, ww // 2, c, _ptr(dr), _stream()),
@@ -1184,6 +1186,8 @@ def nearest_up2_backward_nhwc(d, out=None):
     """tmvs_nearest_up2_backward_nhwc: d [n,2h,2w,C] -> [n,h,w,C] (accumulated into `out` when given)."""
     _dev(d, "d")
     n, h2, w2, c = d.shape
+    if h2 % 2 or w2 % 2:
+        raise ValueError("nearest_up2_backward_nhwc: d must be [n, 2h, 2w, C]")
     y = torch.empty(n, h2 // 2, w2 // 2, c, device=d.device) if out is None else out
     with _Span("tmvs_nearest_up2_backward_nhwc"):
         _lib.check(_lib_h().tmvs_nearest_up2_backward_nhwc(_ptr(d), n, h2 // 2, w2 // 2, c, int(out is not None), _ptr(y),
