@@ -285,6 +285,201 @@ def test_training_primitive_validation_without_gpu(lib):
     assert dm(p, p, p, 16, 2.5, p, lib.tmvs_depth_metrics_workspace(16) - 1, q, None) == ARG
 
 
+def test_training_conv_bn_validation_without_gpu(lib):
+    """The training convolution, weight-gradient and BatchNorm entry points (costreg_train / featurenet_train):
+    null pointers and non-positive extents are TMVS_ERR_ARG, channel counts outside the dispatch tables,
+    stride 3, k of 0 or 8 and a BN channel count that does not divide 256 TMVS_ERR_SHAPE, a workspace one
+    byte short TMVS_ERR_ARG -- all before any launch (the pointers are host memory that is never read; every
+    call below has exactly one thing wrong with it). Entry points that answer differently from their
+    neighbours are pinned with a comment. The workspace formulas are spelled out here and checked either
+    side of their doubling points."""
+    ARG, SHAPE = -1, -2
+    backing = np.zeros(256, np.float32)
+    p = (backing.ctypes.data + 63) & ~63
+    q = p + 256
+    big = 1 << 40
+
+    def blocks(n, per, maxblk):
+        while (n + per - 1) // per > maxblk:
+            per *= 2
+        return -(-n // per)
+
+    # ---- tmvs_conv3d_generic(x, batch, cin, d_in, h_in, w_in, w, cout, d_out, h_out, w_out, stride, flags, y, stream)
+    cg = lib.tmvs_conv3d_generic
+    for nul in range(3):
+        a = [p, p, q]
+        a[nul] = None
+        assert cg(a[0], 1, 8, 2, 2, 2, a[1], 8, 2, 2, 2, 1, 0, a[2], None) == ARG
+    for pos in range(7):  # batch, d_in, h_in, w_in, d_out, h_out, w_out
+        for bad in (0, -1):
+            e = [1, 2, 2, 2, 2, 2, 2]
+            e[pos] = bad
+            assert cg(p, e[0], 8, e[1], e[2], e[3], p, 8, e[4], e[5], e[6], 1, 0, q, None) == ARG, (pos, bad)
+    for flags in (0, 1, 2, 3):
+        for cin, cout in ((3, 8), (8, 3), (0, 8), (8, 0), (-8, 8), (8, -8), (128, 8), (8, 128), (4, 4), (8, 24)):
+            assert cg(p, 1, cin, 2, 2, 2, p, cout, 2, 2, 2, 1, flags, q, None) == SHAPE, (cin, cout)
+        for stride in (0, 3, -1, 4):
+            assert cg(p, 1, 8, 2, 2, 2, p, 8, 2, 2, 2, stride, flags, q, None) == SHAPE
+
+    # ---- tmvs_conv3d_wgrad(direct, a_ch, batch, pd, ph, pw, gathered, b_ch, gd, gh, gw, stride, ws, ws_bytes, dw, stream)
+    wg = lib.tmvs_conv3d_wgrad
+    for nul in range(4):
+        a = [p, p, p, q]
+        a[nul] = None
+        assert wg(a[0], 8, 1, 2, 2, 2, a[1], 8, 2, 2, 2, 1, a[2], big, a[3], None) == ARG
+    for pos in range(7):  # batch, pd, ph, pw, gd, gh, gw
+        for bad in (0, -1):
+            e = [1, 2, 2, 2, 2, 2, 2]
+            e[pos] = bad
+            assert wg(p, 8, e[0], e[1], e[2], e[3], p, 8, e[4], e[5], e[6], 1, p, big, q, None) == ARG, (pos, bad)
+    for stride in (0, 3, -1):
+        assert wg(p, 8, 1, 2, 2, 2, p, 8, 2, 2, 2, stride, p, big, q, None) == SHAPE
+    # the 12 dispatched (direct, gathered) pairs; everything else is TMVS_ERR_SHAPE
+    pairs = {(8, 1), (1, 8), (8, 8), (16, 8), (8, 16), (16, 16), (32, 16), (16, 32), (32, 32), (64, 32), (32, 64),
+             (64, 64)}
+    for a_ch in (0, 1, 3, 8, 16, 32, 64, 128):
+        for b_ch in (0, 1, 3, 8, 16, 32, 64, 128):
+            if (a_ch, b_ch) not in pairs:
+                assert wg(p, a_ch, 1, 2, 2, 2, p, b_ch, 2, 2, 2, 1, p, big, q, None) == SHAPE, (a_ch, b_ch)
+    for a_ch, b_ch in sorted(pairs):
+        need = lib.tmvs_conv3d_wgrad_workspace(1, 2, 3, 5, a_ch, b_ch)
+        assert need == 27 * a_ch * b_ch * 8
+        assert wg(p, a_ch, 1, 2, 3, 5, p, b_ch, 2, 3, 5, 1, p, need - 1, q, None) == ARG
+    V0 = 512 * 2048  # the most voxels 2048-voxel blocks cover with 512 of them
+    for nvox in (1, 90, 2047, 2048, 2049, 2058, 18480, V0 - 1, V0, V0 + 1, 1052969, 2 * V0, 2 * V0 + 1):
+        for a_ch, b_ch in ((8, 1), (8, 8), (64, 64)):
+            want = blocks(nvox, 2048, 512) * 27 * a_ch * b_ch * 8
+            assert lib.tmvs_conv3d_wgrad_workspace(1, 1, 1, nvox, a_ch, b_ch) == want, (nvox, a_ch, b_ch)
+    assert lib.tmvs_conv3d_wgrad_workspace(1, 512, 2048, 1, 8, 8) == 512 * 27 * 64 * 8      # 2048-voxel blocks
+    assert lib.tmvs_conv3d_wgrad_workspace(1, 1, 1, V0 + 1, 8, 8) == 257 * 27 * 64 * 8      # 4096-voxel blocks
+    assert lib.tmvs_conv3d_wgrad_workspace(1, 17, 241, 257, 8, 8) == 258 * 27 * 64 * 8
+    assert lib.tmvs_conv3d_wgrad_workspace(2, 3, 7, 49, 8, 8) == 2 * 27 * 64 * 8            # the batch counts
+
+    # ---- tmvs_conv2d_generic(x, batch, cin, h_in, w_in, w, bias, cout, h_out, w_out, k, stride, pad, flags, y, stream)
+    c2 = lib.tmvs_conv2d_generic
+    for nul in range(3):  # (the bias may be NULL)
+        a = [p, p, q]
+        a[nul] = None
+        assert c2(a[0], 1, 8, 4, 4, a[1], None, 8, 4, 4, 3, 1, 1, 0, a[2], None) == ARG
+    for pos in range(5):  # batch, h_in, w_in, h_out, w_out
+        for bad in (0, -1):
+            e = [1, 4, 4, 4, 4]
+            e[pos] = bad
+            assert c2(p, e[0], 8, e[1], e[2], p, p, 8, e[3], e[4], 3, 1, 1, 0, q, None) == ARG, (pos, bad)
+    for flags in (0, 1, 2, 3):
+        for k in (0, 8, -1):
+            assert c2(p, 1, 8, 4, 4, p, p, 8, 4, 4, k, 1, 1, flags, q, None) == SHAPE
+        for stride in (0, 3, -1):
+            assert c2(p, 1, 8, 4, 4, p, p, 8, 4, 4, 3, stride, 1, flags, q, None) == SHAPE
+        assert c2(p, 1, 8, 4, 4, p, p, 8, 4, 4, 3, 1, -1, flags, q, None) == SHAPE  # pad < 0
+        # cin in {3, 8, 16, 27, 32} with cout % 8 == 0; cin in {8, 16, 32} with cout % 9 == 0
+        for cin, cout in ((4, 8), (0, 8), (-8, 8), (64, 8), (1, 8), (8, 7), (8, 10), (3, 9), (27, 27), (3, 27),
+                          (8, 0), (8, -8), (8, -9)):
+            assert c2(p, 1, cin, 4, 4, p, p, cout, 4, 4, 3, 1, 1, flags, q, None) == SHAPE, (cin, cout)
+
+    # ---- tmvs_conv2d_wgrad(direct, a_ch, batch, ph, pw, gathered, b_ch, gh, gw, k, stride, pad, ws, ws_bytes, dw, stream)
+    w2 = lib.tmvs_conv2d_wgrad
+    for nul in range(4):
+        a = [p, p, p, q]
+        a[nul] = None
+        assert w2(a[0], 8, 1, 4, 4, a[1], 8, 4, 4, 3, 1, 1, a[2], big, a[3], None) == ARG
+    for pos in range(5):  # batch, ph, pw, gh, gw
+        for bad in (0, -1):
+            e = [1, 4, 4, 4, 4]
+            e[pos] = bad
+            assert w2(p, 8, e[0], e[1], e[2], p, 8, e[3], e[4], 3, 1, 1, p, big, q, None) == ARG, (pos, bad)
+    for k in (0, 8, -1):
+        assert w2(p, 8, 1, 4, 4, p, 8, 4, 4, k, 1, 1, p, big, q, None) == SHAPE
+    for stride in (0, 3, -1):
+        assert w2(p, 8, 1, 4, 4, p, 8, 4, 4, 3, stride, 1, p, big, q, None) == SHAPE
+    # a_ch is padded to a multiple of 8: 1..32 with b_ch in {8, 16, 32}, and 8 x 3 (conv0)
+    for a_ch, b_ch in ((0, 8), (33, 8), (64, 8), (8, 0), (8, 4), (8, 64), (16, 3), (8, 27), (9, 3)):
+        assert w2(p, a_ch, 1, 4, 4, p, b_ch, 4, 4, 3, 1, 1, p, big, q, None) == SHAPE, (a_ch, b_ch)
+    assert w2(p, 8, 1, 4, 4, p, 8, 4, 4, 3, 1, 1, p, lib.tmvs_conv2d_wgrad_workspace(1, 4, 4, 8, 8, 3) - 1, q, None) == ARG
+    P0 = 512 * 1024
+    for n in (1, 35, 1023, 1024, 1025, P0 - 1, P0, P0 + 1, 2 * P0, 2 * P0 + 1):
+        for a_ch, b_ch, k in ((8, 3, 3), (27, 32, 3), (16, 8, 5), (9, 16, 1), (32, 32, 7)):
+            want = blocks(n, 1024, 512) * k * k * (-(-a_ch // 8) * 8) * b_ch * 8
+            assert lib.tmvs_conv2d_wgrad_workspace(1, 1, n, a_ch, b_ch, k) == want, (n, a_ch, b_ch, k)
+    assert lib.tmvs_conv2d_wgrad_workspace(1, 512, 1024, 8, 8, 3) == 512 * 9 * 64 * 8
+    assert lib.tmvs_conv2d_wgrad_workspace(1, 1, P0 + 1, 8, 8, 3) == 257 * 9 * 64 * 8
+
+    # ---- BatchNorm: the workspace is [groups][blocks][2][C] partials and [groups][2][C] sums, fp64
+    N0 = 4096 * 1024  # the most voxels 1024-voxel blocks cover with 4096 of them
+
+    def bn_ws(nvox, c):
+        return (blocks(nvox, 1024, 4096) + 1) * 2 * c * 8
+
+    for nvox in (1, 1023, 1024, 1025, N0 - 1, N0, N0 + 1, 2 * N0, 2 * N0 + 1):
+        for c in (1, 4, 8, 64, 256):
+            assert lib.tmvs_bn_train_workspace(nvox, c) == bn_ws(nvox, c), (nvox, c)
+            for groups in (1, 2, 5):
+                assert lib.tmvs_bn_train_workspace_grouped(groups, nvox, c) == groups * bn_ws(nvox, c)
+            for groups in (0, -1):
+                assert lib.tmvs_bn_train_workspace_grouped(groups, nvox, c) == 0
+    assert lib.tmvs_bn_train_workspace(N0, 8) == 4097 * 16 * 8        # 1024-voxel blocks
+    assert lib.tmvs_bn_train_workspace(N0 + 1, 8) == 2050 * 16 * 8    # 2048-voxel blocks
+    assert lib.tmvs_bn_train_workspace_grouped(3, N0 + 1, 8) == 3 * 2050 * 16 * 8
+    not_dividing = (3, 5, 6, 12, 24, 48, 96, 100, 255, 257, 512)
+
+    # ---- tmvs_bn_stats(z, nvox, C, ws, ws_bytes, mean, var, stream); _grouped: groups after z
+    bs, bsg = lib.tmvs_bn_stats, lib.tmvs_bn_stats_grouped
+    for nul in range(4):
+        a = [p, p, q, q]
+        a[nul] = None
+        assert bs(a[0], 16, 8, a[1], big, a[2], a[3], None) == ARG
+        assert bsg(a[0], 2, 16, 8, a[1], big, a[2], a[3], None) == ARG
+    for nvox in (0, -1):
+        assert bs(p, nvox, 8, p, big, q, q, None) == ARG
+        assert bsg(p, 2, nvox, 8, p, big, q, q, None) == ARG
+    for groups in (0, -1):
+        assert bsg(p, groups, 16, 8, p, big, q, q, None) == ARG
+    for c in (0, -8) + not_dividing:  # (a non-positive channel count is a shape here, an argument for the apply below)
+        assert bs(p, 16, c, p, big, q, q, None) == SHAPE, c
+        assert bsg(p, 2, 16, c, p, big, q, q, None) == SHAPE, c
+    assert bs(p, 16, 8, p, bn_ws(16, 8) - 1, q, q, None) == ARG
+    assert bsg(p, 3, 16, 8, p, 3 * bn_ws(16, 8) - 1, q, q, None) == ARG
+
+    # ---- tmvs_bn_relu_train(z, nvox, C, mean, var, gamma, beta, eps, skip, out, stream); _grouped: groups after z
+    bt, btg = lib.tmvs_bn_relu_train, lib.tmvs_bn_relu_train_grouped
+    for nul in range(6):  # (skip may be NULL)
+        a = [p, p, p, p, p, q]
+        a[nul] = None
+        assert bt(a[0], 16, 8, a[1], a[2], a[3], a[4], 1e-5, None, a[5], None) == ARG
+        assert btg(a[0], 2, 16, 8, a[1], a[2], a[3], a[4], 1e-5, None, a[5], None) == ARG
+    for nvox in (0, -1):
+        assert bt(p, nvox, 8, p, p, p, p, 1e-5, None, q, None) == ARG
+        assert btg(p, 2, nvox, 8, p, p, p, p, 1e-5, None, q, None) == ARG
+    for groups in (0, -1):
+        assert btg(p, groups, 16, 8, p, p, p, p, 1e-5, None, q, None) == ARG
+    # PINNED DIFFERENCE: the apply has no workspace and folds `channels <= 0` into its first check, so a
+    # non-positive channel count is TMVS_ERR_ARG here and TMVS_ERR_SHAPE for tmvs_bn_stats / tmvs_bn_relu_backward
+    for c in (0, -8):
+        assert bt(p, 16, c, p, p, p, p, 1e-5, None, q, None) == ARG
+        assert btg(p, 2, 16, c, p, p, p, p, 1e-5, None, q, None) == ARG
+    for c in not_dividing:
+        assert bt(p, 16, c, p, p, p, p, 1e-5, None, q, None) == SHAPE, c
+        assert btg(p, 2, 16, c, p, p, p, p, 1e-5, None, q, None) == SHAPE, c
+
+    # ---- tmvs_bn_relu_backward(dy, z, nvox, C, mean, var, gamma, beta, eps, ws, ws_bytes, dz, dgamma, dbeta, stream)
+    bb, bbg = lib.tmvs_bn_relu_backward, lib.tmvs_bn_relu_backward_grouped
+    for nul in range(10):
+        a = [p, p, p, p, p, p, p, q, q, q]
+        a[nul] = None
+        assert bb(a[0], a[1], 16, 8, a[2], a[3], a[4], a[5], 1e-5, a[6], big, a[7], a[8], a[9], None) == ARG
+        assert bbg(a[0], a[1], 2, 16, 8, a[2], a[3], a[4], a[5], 1e-5, a[6], big, a[7], a[8], a[9], None) == ARG
+    for nvox in (0, -1):
+        assert bb(p, p, nvox, 8, p, p, p, p, 1e-5, p, big, q, q, q, None) == ARG
+        assert bbg(p, p, 2, nvox, 8, p, p, p, p, 1e-5, p, big, q, q, q, None) == ARG
+    for groups in (0, -1):
+        assert bbg(p, p, groups, 16, 8, p, p, p, p, 1e-5, p, big, q, q, q, None) == ARG
+    for c in (0, -8) + not_dividing:
+        assert bb(p, p, 16, c, p, p, p, p, 1e-5, p, big, q, q, q, None) == SHAPE, c
+        assert bbg(p, p, 2, 16, c, p, p, p, p, 1e-5, p, big, q, q, q, None) == SHAPE, c
+    assert bb(p, p, 16, 8, p, p, p, p, 1e-5, p, bn_ws(16, 8) - 1, q, q, q, None) == ARG
+    assert bbg(p, p, 3, 16, 8, p, p, p, p, 1e-5, p, 3 * bn_ws(16, 8) - 1, q, q, q, None) == ARG
+
+
 def test_forward_refuses_cpu_tensors():
     from transmvsnet_amd import TransMVSNet, synthetic
     m = TransMVSNet(ndepths=[8, 8, 8]).eval()

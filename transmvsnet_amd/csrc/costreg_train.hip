@@ -113,255 +113,30 @@ __global__ __launch_bounds__(kTrainBlock) void conv3d_generic_kernel(
 }
 
 // ---------------------------------------------------------------- weight gradient
-// grid (nblk, 27): block (j, k) reduces voxels [j*vpb, (j+1)*vpb) of `direct` for tap k into
-// partial[j][k][A][BC]; thread q owns pairs q, q+256, ... of the A x BC block. Rows of both
-// operands are staged 32 voxels at a time in LDS (a zero row where the tap falls outside).
-template <int A, int BC>
-__global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_kernel(
-    const float* __restrict__ direct, const float* __restrict__ gath, int B, int Pd, int Ph, int Pw, int Gd, int Gh,
-    int Gw, int stride, long vpb, double* __restrict__ partial) {
-  constexpr int NP = (A * BC + kTrainBlock - 1) / kTrainBlock;
-  constexpr int CH = 32;
-  __shared__ __attribute__((aligned(16))) float sd[CH][A];
-  __shared__ __attribute__((aligned(16))) float sg[CH][BC];
-  const int k = blockIdx.y;
-  const int kd = k / 9, kh = (k / 3) % 3, kw = k % 3;
-  const long nvox = (long)B * Pd * Ph * Pw;
-  const long v0 = (long)blockIdx.x * vpb, v1 = v0 + vpb < nvox ? v0 + vpb : nvox;
-  double acc[NP];  // a 32-voxel chunk sums in fp32, chunks in fp64 (BN-normalised gradients cancel)
-#pragma unroll
-  for (int j = 0; j < NP; ++j) acc[j] = 0.0;
-#pragma unroll 1
-  for (long vb = v0; vb < v1; vb += CH) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < CH * A; i += kTrainBlock) {
-      const int r = i / A, a = i % A;
-      const long v = vb + r;
-      sd[r][a] = v < v1 ? direct[v * A + a] : 0.f;
-    }
-    for (int i = threadIdx.x; i < CH * BC; i += kTrainBlock) {
-      const int r = i / BC, c = i % BC;
-      const long v = vb + r;
-      float val = 0.f;
-      if (v < v1) {
-        const int pw = (int)(v % Pw);
-        long t = v / Pw;
-        const int ph = (int)(t % Ph);
-        t /= Ph;
-        const int pd = (int)(t % Pd);
-        const int b = (int)(t / Pd);
-        const int gd = pd * stride - 1 + kd, gh = ph * stride - 1 + kh, gw = pw * stride - 1 + kw;
-        if (gd >= 0 && gh >= 0 && gw >= 0 && gd < Gd && gh < Gh && gw < Gw)
-          val = gath[((((size_t)b * Gd + gd) * Gh + gh) * Gw + gw) * BC + c];
-      }
-      sg[r][c] = val;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      const int q = threadIdx.x + j * kTrainBlock;
-      if (q < A * BC) {
-        const int a = q / BC, c = q % BC;
-        float s = 0.f;
-#pragma unroll 8
-        for (int r = 0; r < CH; ++r) s = fmaf(sd[r][a], sg[r][c], s);
-        acc[j] += (double)s;
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    const int q = threadIdx.x + j * kTrainBlock;
-    if (q < A * BC) partial[((size_t)blockIdx.x * 27 + k) * A * BC + q] = acc[j];
-  }
-}
-
-// Register-tiled form for A, BC >= 8 (the CostRegNet / pathway layers): chunks of 64 voxel rows are
-// staged in LDS (float4, the tap's gather computed once per row quad); wave w takes rows w, w+4, ...;
-// lane (ai, ci) owns the TA x TB block a in [ai*TA, +TA), c in [ci*TB, +TB) (TA = A/8, TB = BC/8), fp32
-// over a chunk's 16 rows then fp64; the 4 waves combine in a fixed order ((w0 + w1) + w2) + w3 through
-// the (then idle) staging LDS.
+// Both channel counts multiples of 8 (the CostRegNet / pathway layers): on the matrix cores. Block
+// (rb, k) of the 1-D grid reduces voxels [rb*vpb, (rb+1)*vpb) of `direct` for tap k into
+// partial[rb][k][A][BC] (tile_reduce_mfma, reduce_mfma.h: 64-row chunks staged in LDS, fp32 within a
+// chunk, fp64 across chunks, the waves combined in a fixed order); a gathered row whose tap falls
+// outside reads as zeros.
 template <int A, int BC>
 __global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_tile_kernel(
     const float* __restrict__ direct, const float* __restrict__ gath, int B, int Pd, int Ph, int Pw, int Gd, int Gh,
     int Gw, int stride, long vpb, int nblk, double* __restrict__ partial) {
+  static_assert(A % 8 == 0 && BC % 8 == 0, "the matrix-core tile takes multiples of 8");
   int rb, k;  // the 27 taps of a voxel range on one XCD (common.h)
   if (!xcd_range_tap(27, nblk, rb, k)) return;
   const int kd = k / 9, kh = (k / 3) % 3, kw = k % 3;
-  if constexpr (A % 8 == 0 && BC % 8 == 0) {  // on the matrix cores (reduce_mfma.h)
-    const long nv = (long)B * Pd * Ph * Pw;
-    const long u0 = (long)rb * vpb, u1 = u0 + vpb < nv ? u0 + vpb : nv;
-    auto la = [&](long v, int q) { return *reinterpret_cast<const float4*>(direct + v * A + 4 * q); };
-    auto lb = [&](long v, int q) {
-      int b, pd, ph, pw;
-      chunk_row_coords3(v, Pd, Ph, Pw, b, pd, ph, pw);  // rows of 64-aligned chunks (wgrad_vpb: multiples of 2048)
-      const int gd = pd * stride - 1 + kd, gh = ph * stride - 1 + kh, gw = pw * stride - 1 + kw;
-      if (gd < 0 || gh < 0 || gw < 0 || gd >= Gd || gh >= Gh || gw >= Gw) return make_float4(0.f, 0.f, 0.f, 0.f);
-      return *reinterpret_cast<const float4*>(gath + ((((size_t)b * Gd + gd) * Gh + gh) * Gw + gw) * BC + 4 * q);
-    };
-    tile_reduce_mfma<A, BC>(u0, u1, la, lb, partial + ((size_t)rb * 27 + k) * A * BC);
-    return;
-  }
-  constexpr int CH = 64, TA = A / 8, TB = BC / 8, SA = A + 4, SB = BC + 4;
-  static_assert(A >= 8 && BC >= 8, "tile kernel needs 8 x 8 lanes");
-  static_assert(CH * (SA + SB) * 4 >= A * BC * 8, "combine buffer fits the staging LDS");
-  __shared__ __attribute__((aligned(16))) float lds[CH * (SA + SB)];
-  float* sd = lds;
-  float* sg = lds + CH * SA;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int ci = lane & 7, ai = lane >> 3;
-  const long nvox = (long)B * Pd * Ph * Pw;
-  const long v0 = (long)rb * vpb, v1 = v0 + vpb < nvox ? v0 + vpb : nvox;
-  double acc[TA][TB];
-#pragma unroll
-  for (int i = 0; i < TA; ++i)
-#pragma unroll
-    for (int j = 0; j < TB; ++j) acc[i][j] = 0.0;
-#pragma unroll 1
-  for (long vb = v0; vb < v1; vb += CH) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < CH * A / 4; i += kTrainBlock) {
-      const int r = i / (A / 4), c = (i % (A / 4)) * 4;
-      const long v = vb + r;
-      *reinterpret_cast<float4*>(sd + r * SA + c) =
-          v < v1 ? *reinterpret_cast<const float4*>(direct + v * A + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    // the chunk's first voxel once (wave-uniform), then each row by carrying from it
-    const int pw0 = (int)(vb % Pw);
-    const long t0 = vb / Pw;
-    const int ph0 = (int)(t0 % Ph), pd0 = (int)((t0 / Ph) % Pd), b0 = (int)(t0 / ((long)Ph * Pd));
-    for (int i = threadIdx.x; i < CH * BC / 4; i += kTrainBlock) {
-      const int r = i / (BC / 4), c = (i % (BC / 4)) * 4;
-      const long v = vb + r;
-      float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (v < v1) {
-        int pw = pw0 + r, ph = ph0, pd = pd0, b = b0;
-        while (pw >= Pw) {
-          pw -= Pw;
-          if (++ph == Ph) {
-            ph = 0;
-            if (++pd == Pd) {
-              pd = 0;
-              ++b;
-            }
-          }
-        }
-        const int gd = pd * stride - 1 + kd, gh = ph * stride - 1 + kh, gw = pw * stride - 1 + kw;
-        if (gd >= 0 && gh >= 0 && gw >= 0 && gd < Gd && gh < Gh && gw < Gw)
-          val = *reinterpret_cast<const float4*>(gath + ((((size_t)b * Gd + gd) * Gh + gh) * Gw + gw) * BC + c);
-      }
-      *reinterpret_cast<float4*>(sg + r * SB + c) = val;
-    }
-    __syncthreads();
-    float s[TA][TB];
-#pragma unroll
-    for (int i = 0; i < TA; ++i)
-#pragma unroll
-      for (int j = 0; j < TB; ++j) s[i][j] = 0.f;
-#pragma unroll 4
-    for (int r = wv; r < CH; r += 4) {
-      float av[TA], bv[TB];
-#pragma unroll
-      for (int i = 0; i < TA; ++i) av[i] = sd[r * SA + ai * TA + i];
-#pragma unroll
-      for (int j = 0; j < TB; ++j) bv[j] = sg[r * SB + ci * TB + j];
-#pragma unroll
-      for (int i = 0; i < TA; ++i)
-#pragma unroll
-        for (int j = 0; j < TB; ++j) s[i][j] = fmaf(av[i], bv[j], s[i][j]);
-    }
-#pragma unroll
-    for (int i = 0; i < TA; ++i)
-#pragma unroll
-      for (int j = 0; j < TB; ++j) acc[i][j] += (double)s[i][j];
-  }
-  double* cmb = reinterpret_cast<double*>(lds);
-#pragma unroll 1
-  for (int w = 1; w < 4; ++w) {
-    __syncthreads();
-    if (wv == w)
-#pragma unroll
-      for (int i = 0; i < TA; ++i)
-#pragma unroll
-        for (int j = 0; j < TB; ++j) cmb[(ai * TA + i) * BC + ci * TB + j] = acc[i][j];
-    __syncthreads();
-    if (wv == 0)
-#pragma unroll
-      for (int i = 0; i < TA; ++i)
-#pragma unroll
-        for (int j = 0; j < TB; ++j) acc[i][j] += cmb[(ai * TA + i) * BC + ci * TB + j];
-  }
-  if (wv == 0) {
-    double* out = partial + ((size_t)rb * 27 + k) * A * BC;
-#pragma unroll
-    for (int i = 0; i < TA; ++i)
-#pragma unroll
-      for (int j = 0; j < TB; ++j) out[(ai * TA + i) * BC + ci * TB + j] = acc[i][j];
-  }
-}
-
-// Few (a, b) pairs (conv0: 8 x 1, prob: 1 x 8): voxel-parallel instead -- thread t takes voxels
-// t, t+256, ... of the block's range straight from global memory and accumulates all A*BC pairs, then
-// a fixed LDS tree per pair.
-template <int A, int BC>
-__global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_small_kernel(
-    const float* __restrict__ direct, const float* __restrict__ gath, int B, int Pd, int Ph, int Pw, int Gd, int Gh,
-    int Gw, int stride, long vpb, double* __restrict__ partial) {
-  constexpr int NPR = A * BC;
-  __shared__ double red[NPR][kTrainBlock];
-  const int k = blockIdx.y;
-  const int kd = k / 9, kh = (k / 3) % 3, kw = k % 3;
-  const long nvox = (long)B * Pd * Ph * Pw;
-  const long v0 = (long)blockIdx.x * vpb, v1 = v0 + vpb < nvox ? v0 + vpb : nvox;
-  double acc[NPR];
-#pragma unroll
-  for (int q = 0; q < NPR; ++q) acc[q] = 0.0;
-  // voxel coordinates advance incrementally (one division per thread, not three per voxel)
-  long v = v0 + threadIdx.x;
-  int pw = (int)(v % Pw), ph, pd, b;
-  {
-    const long t = v / Pw;
-    ph = (int)(t % Ph);
-    pd = (int)((t / Ph) % Pd);
-    b = (int)(t / ((long)Ph * Pd));
-  }
-  for (; v < v1; v += kTrainBlock) {
+  const long nv = (long)B * Pd * Ph * Pw;
+  const long u0 = (long)rb * vpb, u1 = u0 + vpb < nv ? u0 + vpb : nv;
+  auto la = [&](long v, int q) { return *reinterpret_cast<const float4*>(direct + v * A + 4 * q); };
+  auto lb = [&](long v, int q) {
+    int b, pd, ph, pw;
+    chunk_row_coords3(v, Pd, Ph, Pw, b, pd, ph, pw);  // rows of 64-aligned chunks (wgrad_vpb: multiples of 2048)
     const int gd = pd * stride - 1 + kd, gh = ph * stride - 1 + kh, gw = pw * stride - 1 + kw;
-    const bool ok = gd >= 0 && gh >= 0 && gw >= 0 && gd < Gd && gh < Gh && gw < Gw;
-    const long vv = v;
-    const float* gp = gath + ((((size_t)b * Gd + gd) * Gh + gh) * Gw + gw) * BC;  // used only when ok
-    pw += kTrainBlock;
-    while (pw >= Pw) {
-      pw -= Pw;
-      if (++ph == Ph) {
-        ph = 0;
-        if (++pd == Pd) {
-          pd = 0;
-          ++b;
-        }
-      }
-    }
-    if (!ok) continue;
-    float dv[A], gv[BC];
-#pragma unroll
-    for (int a = 0; a < A; ++a) dv[a] = direct[vv * A + a];
-#pragma unroll
-    for (int c = 0; c < BC; ++c) gv[c] = gp[c];
-#pragma unroll
-    for (int a = 0; a < A; ++a)
-#pragma unroll
-      for (int c = 0; c < BC; ++c) acc[a * BC + c] += (double)(dv[a] * gv[c]);
-  }
-#pragma unroll
-  for (int q = 0; q < NPR; ++q) red[q][threadIdx.x] = acc[q];
-  __syncthreads();
-  for (int st = kTrainBlock / 2; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st)
-#pragma unroll
-      for (int q = 0; q < NPR; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + st];
-    __syncthreads();
-  }
-  if ((int)threadIdx.x < NPR) partial[((size_t)blockIdx.x * 27 + k) * NPR + threadIdx.x] = red[threadIdx.x][0];
+    if (gd < 0 || gh < 0 || gw < 0 || gd >= Gd || gh >= Gh || gw >= Gw) return make_float4(0.f, 0.f, 0.f, 0.f);
+    return *reinterpret_cast<const float4*>(gath + ((((size_t)b * Gd + gd) * Gh + gh) * Gw + gw) * BC + 4 * q);
+  };
+  tile_reduce_mfma<A, BC>(u0, u1, la, lb, partial + ((size_t)rb * 27 + k) * A * BC);
 }
 
 // Few (a, b) pairs, one kd plane of taps per block row (grid.y = 3): a thread reads its voxel's
@@ -821,18 +596,14 @@ static int launch_wgrad(const float* direct, const float* gath, int B, int Pd, i
   const long nvox = (long)B * Pd * Ph * Pw;
   const long vpb = wgrad_vpb(nvox);
   const int nblk = (int)((nvox + vpb - 1) / vpb);
+  // the taps kernel for the few-pair layers (conv0: 8 x 1, prob: 1 x 8), the matrix-core tile otherwise
+  static_assert(A * BC <= 8 || (A % 8 == 0 && BC % 8 == 0), "no weight-gradient kernel for this channel pair");
   if constexpr (A * BC <= 8)
     hipLaunchKernelGGL((conv3d_wgrad_taps_kernel<A, BC>), dim3(nblk, 3), dim3(kTrainBlock), 0, st, direct, gath, B,
                        Pd, Ph, Pw, Gd, Gh, Gw, stride, vpb, ws);
-  else if constexpr (A * BC <= 16)
-    hipLaunchKernelGGL((conv3d_wgrad_small_kernel<A, BC>), dim3(nblk, 27), dim3(kTrainBlock), 0, st, direct, gath, B,
-                       Pd, Ph, Pw, Gd, Gh, Gw, stride, vpb, ws);
-  else if constexpr (A >= 8 && BC >= 8)
+  else
     hipLaunchKernelGGL((conv3d_wgrad_tile_kernel<A, BC>), xcd_range_tap_grid(27, nblk), dim3(kTrainBlock), 0, st, direct,
                        gath, B, Pd, Ph, Pw, Gd, Gh, Gw, stride, vpb, nblk, ws);
-  else
-    hipLaunchKernelGGL((conv3d_wgrad_kernel<A, BC>), dim3(nblk, 27), dim3(kTrainBlock), 0, st, direct, gath, B, Pd,
-                       Ph, Pw, Gd, Gh, Gw, stride, vpb, ws);
   TMVS_CHECK_LAUNCH();
   const long n = 27L * A * BC;
   hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((n + 31) / 32)), dim3(kTrainBlock), 0,
@@ -951,6 +722,7 @@ extern "C" int tmvs_bn_relu_train_grouped(const float* z, int groups, long nvox,
                                           const float* skip, float* out, void* stream) {
   if (!z || !mean || !var || !gamma || !beta || !out || nvox <= 0 || channels <= 0 || groups <= 0)
     return TMVS_ERR_ARG;
+  if (kTrainBlock % channels) return TMVS_ERR_SHAPE;  // as the statistics and the backward: C divides 256
   const long per = nvox * channels, n = per * groups;
   if (channels % 4 == 0 && aligned16(z) && aligned16(out) && (!skip || aligned16(skip))) {
     const long n4 = n / 4;

@@ -779,7 +779,7 @@ extern "C" int tmvs_conv2d_generic(const float* x, int batch, int cin, int h_in,
                                    const float* bias, int cout, int h_out, int w_out, int k, int stride, int pad,
                                    int flags, float* y, void* stream) {
   if (!x || !w || !y || batch <= 0 || h_in <= 0 || w_in <= 0 || h_out <= 0 || w_out <= 0) return TMVS_ERR_ARG;
-  if (k < 1 || k > 7 || (stride != 1 && stride != 2) || pad < 0) return TMVS_ERR_SHAPE;
+  if (k < 1 || k > 7 || (stride != 1 && stride != 2) || pad < 0 || cout <= 0) return TMVS_ERR_SHAPE;
   const int tr = (flags & TMVS_CONV_TRANSPOSED) ? 1 : 0, acc = (flags & TMVS_CONV_ACCUMULATE) ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
   const long np = (long)batch * h_out * w_out;

@@ -602,6 +602,8 @@ def conv3d_generic(x, w_packed, cout, out_dhw, stride, transposed=False, out=Non
     _dev(x, "x")
     _dev(w_packed, "w_packed")
     b, d, h, w, cin = x.shape
+    if w_packed.numel() != 27 * cout * cin:
+        raise ValueError("conv3d_generic: w_packed must hold [27, cout, cin] floats")
     flags = (_lib.CONV_TRANSPOSED if transposed else 0) | (_lib.CONV_ACCUMULATE if out is not None else 0)
     y = torch.empty(b, *out_dhw, cout, device=x.device) if out is None else out
     if tuple(y.shape) != (b, *out_dhw, cout) or not y.is_contiguous():
@@ -657,7 +659,9 @@ def conv3d_wgrad(direct, gathered, stride):
     _dev(direct, "direct")
     _dev(gathered, "gathered")
     b, pd, ph, pw, a = direct.shape
-    _, gd, gh, gw, bc = gathered.shape
+    gb, gd, gh, gw, bc = gathered.shape
+    if gb != b:
+        raise ValueError("conv3d_wgrad: direct and gathered must have the same batch size")
     nbytes = _lib_h().tmvs_conv3d_wgrad_workspace(b, pd, ph, pw, a, bc)
     ws = torch.empty(nbytes // 4 + 64, device=direct.device)
     dw = torch.empty(27, a, bc, device=direct.device)
@@ -665,6 +669,18 @@ def conv3d_wgrad(direct, gathered, stride):
         _lib.check(_lib_h().tmvs_conv3d_wgrad(_ptr(direct), a, b, pd, ph, pw, _ptr(gathered), bc, gd, gh, gw, stride,
                                               _ptr(ws), ws.numel() * 4, _ptr(dw), _stream()), "tmvs_conv3d_wgrad")
     return dw
+
+
+def _bn_shapes(what, z, per_channel, like_z, groups=1):
+    """the statistics / affine vectors hold groups * C (or C) floats and the element-wise tensors z's count:
+    the entry points take one size for all of them"""
+    c = z.shape[-1]
+    for name, t, n in per_channel:
+        if t.numel() != n * c:
+            raise ValueError(f"{what}: {name} must hold {n * c} floats")
+    for name, t in like_z:
+        if t is not None and t.numel() != z.numel():
+            raise ValueError(f"{what}: {name} must have z's size")
 
 
 def _bn_ws(nvox, c, device):
@@ -690,6 +706,8 @@ def bn_relu_train(z, mean, var, gamma, beta, eps, skip=None, out=None):
     for t, n in ((z, "z"), (mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta"), (skip, "skip"), (out, "out")):
         _dev(t, n)
     c = z.shape[-1]
+    _bn_shapes("bn_relu_train", z, (("mean", mean, 1), ("var", var, 1), ("gamma", gamma, 1), ("beta", beta, 1)),
+               (("skip", skip), ("out", out)))
     out = torch.empty_like(z) if out is None else out
     with _Span("tmvs_bn_relu_train"):
         _lib.check(_lib_h().tmvs_bn_relu_train(_ptr(z), z.numel() // c, c, _ptr(mean), _ptr(var), _ptr(gamma),
@@ -703,6 +721,8 @@ def bn_relu_backward(dy, z, mean, var, gamma, beta, eps, dz=None):
     for t, n in ((dy, "dy"), (z, "z"), (mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta"), (dz, "dz")):
         _dev(t, n)
     c = z.shape[-1]
+    _bn_shapes("bn_relu_backward", z, (("mean", mean, 1), ("var", var, 1), ("gamma", gamma, 1), ("beta", beta, 1)),
+               (("dy", dy), ("dz", dz)))
     nvox = z.numel() // c
     ws = _bn_ws(nvox, c, z.device)
     dz = torch.empty_like(z) if dz is None else dz
@@ -734,6 +754,8 @@ def bn_relu_train_grouped(z, mean, var, gamma, beta, eps):
     for t, n in ((z, "z"), (mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta")):
         _dev(t, n)
     g, c = z.shape[0], z.shape[-1]
+    _bn_shapes("bn_relu_train_grouped", z, (("mean", mean, g), ("var", var, g), ("gamma", gamma, 1), ("beta", beta, 1)),
+               ())
     out = torch.empty_like(z)
     with _Span("tmvs_bn_relu_train_grouped"):
         _lib.check(_lib_h().tmvs_bn_relu_train_grouped(_ptr(z), g, z.numel() // (g * c), c, _ptr(mean), _ptr(var),
@@ -747,6 +769,8 @@ def bn_relu_backward_grouped(dy, z, mean, var, gamma, beta, eps):
     for t, n in ((dy, "dy"), (z, "z"), (mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta")):
         _dev(t, n)
     g, c = z.shape[0], z.shape[-1]
+    _bn_shapes("bn_relu_backward_grouped", z,
+               (("mean", mean, g), ("var", var, g), ("gamma", gamma, 1), ("beta", beta, 1)), (("dy", dy),))
     nvox = z.numel() // (g * c)
     ws = torch.empty(_lib_h().tmvs_bn_train_workspace_grouped(g, nvox, c) // 4 + 64, device=z.device)
     dz = torch.empty_like(z)
@@ -1063,6 +1087,8 @@ def conv2d_generic(x, w_taps, cout, out_hw, k, stride, pad, bias=None, transpose
     _dev(w_taps, "w_taps")
     _dev(bias, "bias")
     b, h, w, cin = x.shape
+    if w_taps.numel() != k * k * cout * cin or (bias is not None and bias.numel() != cout):
+        raise ValueError("conv2d_generic: w_taps must hold [k*k, cout, cin] floats and bias [cout]")
     flags = (_lib.CONV_TRANSPOSED if transposed else 0) | (_lib.CONV_ACCUMULATE if out is not None else 0)
     y = torch.empty(b, *out_hw, cout, device=x.device) if out is None else out
     if tuple(y.shape) != (b, *out_hw, cout) or not y.is_contiguous():
@@ -1079,7 +1105,9 @@ def conv2d_wgrad(direct, gathered, k, stride, pad):
     _dev(direct, "direct")
     _dev(gathered, "gathered")
     b, ph, pw, a = direct.shape
-    _, gh, gw, bc = gathered.shape
+    gb, gh, gw, bc = gathered.shape
+    if gb != b:
+        raise ValueError("conv2d_wgrad: direct and gathered must have the same batch size")
     nbytes = _lib_h().tmvs_conv2d_wgrad_workspace(b, ph, pw, a, bc, k)
     ws = torch.empty(nbytes // 4 + 64, device=direct.device)
     dw = torch.empty(k * k, a, bc, device=direct.device)
