@@ -480,6 +480,134 @@ def test_training_conv_bn_validation_without_gpu(lib):
     assert bbg(p, p, 3, 16, 8, p, p, p, p, 1e-5, p, 3 * bn_ws(16, 8) - 1, q, q, q, None) == ARG
 
 
+def test_inference_costreg_validation_without_gpu(lib):
+    """The inference CostRegNet and softmax / WTA entry points (costreg / glue): the status each returns before
+    any launch, as the library answers today (the pointers are host memory that is never read; every call
+    below has exactly one thing wrong with it). tmvs_conv3d_mfma asks for the device before it dispatches and
+    is left out."""
+    ARG, SHAPE = -1, -2
+    backing = np.zeros(256, np.float32)
+    p = (backing.ctypes.data + 63) & ~63
+    q = p + 256
+
+    # ---- tmvs_conv3d_bn_relu(x, batch, cin, d, h, w, wpk, alpha, shift, cout, stride, y, stream)
+    cb = lib.tmvs_conv3d_bn_relu
+    for nul in range(5):
+        a = [p, p, p, p, q]
+        a[nul] = None
+        assert cb(a[0], 1, 16, 2, 2, 2, a[1], a[2], a[3], 16, 1, a[4], None) == ARG
+    for pos in range(4):  # batch, d, h, w
+        for bad in (0, -1):
+            e = [1, 2, 2, 2]
+            e[pos] = bad
+            assert cb(p, e[0], 16, e[1], e[2], e[3], p, p, p, 16, 1, q, None) == ARG, (pos, bad)
+    for stride in (0, 3, -1):  # a bad enum: TMVS_ERR_ARG (tmvs_conv3d_generic answers TMVS_ERR_SHAPE)
+        assert cb(p, 1, 16, 2, 2, 2, p, p, p, 16, stride, q, None) == ARG
+    conv_pairs = {(16, 16, 1), (32, 32, 1), (64, 64, 1), (8, 16, 2), (16, 32, 2), (32, 64, 2)}
+    for cin in (0, 1, 8, 16, 32, 64, 128):
+        for cout in (0, 1, 8, 16, 32, 64, 128):
+            for stride in (1, 2):
+                if (cin, cout, stride) not in conv_pairs:
+                    assert cb(p, 1, cin, 2, 2, 2, p, p, p, cout, stride, q, None) == SHAPE, (cin, cout, stride)
+    # one sample's input of 2 GiB or more (32-bit byte offsets): 16 channels x 4 bytes x 2^25 voxels
+    assert cb(p, 1, 16, 32, 1024, 1024, p, p, p, 16, 1, q, None) == SHAPE
+    assert cb(p, 1, 8, 64, 1024, 1024, p, p, p, 16, 2, q, None) == SHAPE
+
+    # ---- tmvs_deconv3d_bn_relu_add(x, batch, cin, d, h, w, wpk, alpha, shift, cout, skip, y, stream)
+    db = lib.tmvs_deconv3d_bn_relu_add
+    for nul in range(6):  # (the skip is required here; tmvs_conv3d_mfma's is nullable)
+        a = [p, p, p, p, p, q]
+        a[nul] = None
+        assert db(a[0], 1, 16, 2, 2, 2, a[1], a[2], a[3], 8, a[4], a[5], None) == ARG
+    for pos in range(4):
+        for bad in (0, -1):
+            e = [1, 2, 2, 2]
+            e[pos] = bad
+            assert db(p, e[0], 16, e[1], e[2], e[3], p, p, p, 8, p, q, None) == ARG, (pos, bad)
+    deconv_pairs = {(64, 32), (32, 16), (16, 8)}
+    for cin in (0, 1, 8, 16, 32, 64, 128):
+        for cout in (0, 1, 8, 16, 32, 64, 128):
+            if (cin, cout) not in deconv_pairs:
+                assert db(p, 1, cin, 2, 2, 2, p, p, p, cout, p, q, None) == SHAPE, (cin, cout)
+
+    # ---- tmvs_costregnet_workspace: conv0, conv1, conv2, ..., x7, x9, x11, each rounded up to 256 bytes
+    def ws_bytes(b, d, h, w, c=8):
+        up = lambda n: (n + 255) & ~255
+        v0 = b * d * h * w
+        v1, v2, v3 = v0 // 8, v0 // 64, v0 // 512
+        return (2 * up(v0 * c * 4) + 3 * up(v1 * 2 * c * 4) + 3 * up(v2 * 4 * c * 4) + 2 * up(v3 * 8 * c * 4))
+
+    assert lib.tmvs_costregnet_workspace(2, 8, 24, 40, 8) == ws_bytes(2, 8, 24, 40) == 1459200
+    assert lib.tmvs_costregnet_workspace(1, 4, 4, 4, 8) == ws_bytes(1, 4, 4, 4) == 6400  # the 256-byte rounding
+
+    # ---- tmvs_costregnet(x, batch, depth, height, width, weights, workspace, workspace_bytes, logits, stream)
+    #      tmvs_costregnet_wta(x, hyp, batch, depth, height, width, weights, workspace, workspace_bytes,
+    #                          clamp_lo, clamp_hi, prob, depth_out, depth_raw, conf, stream)
+    def weights(base_ch=8, null=None):
+        st = _lib.CostRegWeights()
+        for i in range(11):
+            st.w[i] = p
+        for i in range(10):
+            st.alpha[i] = p
+            st.shift[i] = p
+        if null is not None:
+            getattr(st, null[0])[null[1]] = None
+        st.base_ch = base_ch
+        return st
+
+    cr, cw = lib.tmvs_costregnet, lib.tmvs_costregnet_wta
+    good = weights()
+    need = ws_bytes(1, 8, 8, 8)
+
+    def both(x=p, hyp=p, b=1, d=8, h=8, w=8, st=good, ws=p, nbytes=need, out=q):
+        """(tmvs_costregnet, tmvs_costregnet_wta) on the same arguments"""
+        ref = None if st is None else ctypes.byref(st)
+        return (cr(x, b, d, h, w, ref, ws, nbytes, out, None),
+                cw(x, hyp, b, d, h, w, ref, ws, nbytes, 425.0, 935.0, out, q, q, q, None))
+
+    assert both(x=None) == (ARG, ARG) and both(st=None) == (ARG, ARG) and both(ws=None) == (ARG, ARG)
+    assert both(out=None) == (ARG, ARG)
+    assert cw(p, None, 1, 8, 8, 8, ctypes.byref(good), p, need, 425.0, 935.0, q, q, q, q, None) == ARG
+    for nul in range(3):  # depth_out, depth_raw, conf
+        a = [q, q, q]
+        a[nul] = None
+        assert cw(p, p, 1, 8, 8, 8, ctypes.byref(good), p, need, 425.0, 935.0, q, a[0], a[1], a[2], None) == ARG
+    for b in (0, -1):
+        assert both(b=b) == (ARG, ARG)
+    for null in (("w", 0), ("w", 10), ("alpha", 0), ("alpha", 9), ("shift", 0), ("shift", 9)):
+        assert both(st=weights(null=null)) == (ARG, ARG), null
+    for bad in (4, 12, 20, 7):  # a depth, height or width that is no multiple of 8
+        assert both(h=bad) == (SHAPE, SHAPE) and both(w=bad) == (SHAPE, SHAPE)
+    for bad in (4, 12, 20, 7):
+        assert both(d=bad) == (SHAPE, SHAPE)
+    for base_ch in (0, 4, 16, -8):
+        assert both(st=weights(base_ch)) == (SHAPE, SHAPE), base_ch
+    # one sample's 8-channel full-resolution volume of 2 GiB or more
+    assert both(d=64, h=1024, w=1024, nbytes=1 << 40) == (SHAPE, SHAPE)
+    assert both(nbytes=need - 1) == (ARG, ARG)
+    assert both(nbytes=0) == (ARG, ARG)
+    # the WTA form takes the depths tmvs_softmax_wta has an instance for: 40 and 56 are multiples of 8 that
+    # the plain form accepts and it does not
+    for d in (40, 56, 72, 128, 0, -8):
+        assert cw(p, p, 1, d, 8, 8, ctypes.byref(good), p, 1 << 40, 425.0, 935.0, q, q, q, q, None) == SHAPE, d
+
+    # ---- tmvs_softmax_wta(logits, hyp, batch, ndepth, height, width, clamp_lo, clamp_hi, prob, depth, depth_raw,
+    #                       conf, stream)
+    sw = lib.tmvs_softmax_wta
+    for nul in range(6):
+        a = [p, p, q, q, q, q]
+        a[nul] = None
+        assert sw(a[0], a[1], 1, 8, 2, 2, 425.0, 935.0, a[2], a[3], a[4], a[5], None) == ARG
+    for pos in range(3):  # batch, height, width
+        for bad in (0, -1):
+            e = [1, 2, 2]
+            e[pos] = bad
+            assert sw(p, p, e[0], 8, e[1], e[2], 425.0, 935.0, q, q, q, q, None) == ARG, (pos, bad)
+    # the depths without an instance, 0 and negative ones included, are a shape
+    for d in (12, 40, 0, -8, 1, 2, 56, 128):
+        assert sw(p, p, 1, d, 2, 2, 425.0, 935.0, q, q, q, q, None) == SHAPE, d
+
+
 def test_forward_refuses_cpu_tensors():
     from transmvsnet_amd import TransMVSNet, synthetic
     m = TransMVSNet(ndepths=[8, 8, 8]).eval()

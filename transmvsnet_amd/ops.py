@@ -281,19 +281,71 @@ def costregnet_wta(x, weights: "_lib.CostRegWeights", hyp, clamp=(425.0, 935.0))
     return prob, depth, raw, conf
 
 
-def conv3d_bn_relu(x, wpk, alpha, shift, cout, stride):
+def _layer_args(op, x, wpk, alpha, shift, cout):
+    """What the single-layer entry points cannot see and would read past: every tensor contiguous fp32 on
+    x's device, 27 * cout * cin packed weights, cout floats of alpha / shift (None: the raw epilogue)."""
+    if x.dim() != 5:
+        raise ValueError(f"{op}: x must be NDHWC [B, D, H, W, cin]")
+    for name, t in (("x", x), ("wpk", wpk), ("alpha", alpha), ("shift", shift)):
+        _layer_tensor(op, name, t, x.device)
+    cin = x.shape[4]
+    if wpk.numel() != 27 * cout * cin:
+        raise ValueError(f"{op}: wpk must hold 27 * cout * cin = {27 * cout * cin} floats, not {wpk.numel()}")
+    for name, t in (("alpha", alpha), ("shift", shift)):
+        if t is not None and t.numel() < cout:
+            raise ValueError(f"{op}: {name} must hold cout = {cout} floats, not {t.numel()}")
+
+
+def _layer_tensor(op, name, t, device):
+    if t is None:
+        return
+    if not t.is_cuda or t.device != device:
+        raise ValueError(f"{op}: {name} must be a GPU tensor on x's device (the HIP path has no CPU fallback)")
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{op}: {name} must be contiguous float32")
+
+
+def _layer_like(op, name, t, shape, device):
+    """`t` (skip or out, may be None) is a contiguous fp32 device tensor of `shape`"""
+    _layer_tensor(op, name, t, device)
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{op}: {name} must be a contiguous {list(shape)} tensor, not {list(t.shape)}")
+
+
+def _layer_no_alias(op, skip, out):
+    if skip is not None and out is not None and skip.data_ptr() == out.data_ptr():
+        raise ValueError(f"{op}: out must not alias skip (the kernels read skip while they write out)")
+
+
+def _conv_out_dhw(d, h, w, stride):
+    return (d, h, w) if stride == 1 else ((d - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
+
+
+def conv3d_bn_relu(x, wpk, alpha, shift, cout, stride, out=None):
+    """tmvs_conv3d_bn_relu: x NDHWC, wpk [27][cout][cin] -> relu(conv * alpha + shift), written to `out` when given."""
+    _layer_args("conv3d_bn_relu", x, wpk, alpha, shift, cout)
     b, d, h, w, cin = x.shape
-    do, ho, wo = ((d - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1) if stride == 2 else (d, h, w)
-    y = torch.empty(b, do, ho, wo, cout, device=x.device)
+    shape = (b, *_conv_out_dhw(d, h, w, stride), cout)
+    _layer_like("conv3d_bn_relu", "out", out, shape, x.device)
+    y = torch.empty(shape, device=x.device) if out is None else out
     with _Span("tmvs_conv3d_bn_relu"):
         _lib.check(_lib_h().tmvs_conv3d_bn_relu(_ptr(x), b, cin, d, h, w, _ptr(wpk), _ptr(alpha), _ptr(shift), cout,
                                                 stride, _ptr(y), _stream()), "tmvs_conv3d_bn_relu")
     return y
 
 
-def deconv3d_bn_relu_add(x, wpk, alpha, shift, cout, skip):
+def deconv3d_bn_relu_add(x, wpk, alpha, shift, cout, skip, out=None):
+    """tmvs_deconv3d_bn_relu_add: skip + relu(conv_transpose * alpha + shift) at twice x's extents, written to
+    `out` (not skip itself) when given."""
+    _layer_args("deconv3d_bn_relu_add", x, wpk, alpha, shift, cout)
     b, d, h, w, cin = x.shape
-    y = torch.empty(b, 2 * d, 2 * h, 2 * w, cout, device=x.device)
+    shape = (b, 2 * d, 2 * h, 2 * w, cout)
+    if skip is None:
+        raise ValueError("deconv3d_bn_relu_add: skip is required")
+    _layer_like("deconv3d_bn_relu_add", "skip", skip, shape, x.device)
+    _layer_like("deconv3d_bn_relu_add", "out", out, shape, x.device)
+    _layer_no_alias("deconv3d_bn_relu_add", skip, out)
+    y = torch.empty(shape, device=x.device) if out is None else out
     with _Span("tmvs_deconv3d_bn_relu_add"):
         _lib.check(_lib_h().tmvs_deconv3d_bn_relu_add(_ptr(x), b, cin, d, h, w, _ptr(wpk), _ptr(alpha), _ptr(shift),
                                                       cout, _ptr(skip), _ptr(y), _stream()), "tmvs_deconv3d_bn_relu_add")
@@ -628,28 +680,24 @@ def prob_pack(w27):
     return torch.cat([pairs, single], 1).contiguous()
 
 
-def conv3d_mfma(x, w_packed, cout, stride, transposed=False, skip=None):
+def conv3d_mfma(x, w_packed, cout, stride, transposed=False, skip=None, out=None):
     """tmvs_conv3d_mfma: x NDHWC [B,D,H,W,Cin], w_packed [27][cout][Cin] -> y [B,D',H',W',cout], the raw
     convolution (no BN / ReLU) on the inference MFMA kernels; transposed = ConvTranspose3d k3 s2 p1 op1
-    (+ skip, a separate [B,2D,2H,2W,cout] tensor)."""
-    _dev(x, "x")
-    _dev(w_packed, "w_packed")
-    _dev(skip, "skip")
+    (+ skip, a separate [B,2D,2H,2W,cout] tensor). Written to `out` when given."""
+    _layer_args("conv3d_mfma", x, w_packed, None, None, cout)
     b, d, h, w, cin = x.shape
-    if transposed:
-        dims = (2 * d, 2 * h, 2 * w)
-    else:
-        dims = (d, h, w) if stride == 1 else ((d - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
-    y = torch.empty(b, *dims, cout, device=x.device)
-    if skip is not None and (tuple(skip.shape) != tuple(y.shape) or not skip.is_contiguous()):
-        raise ValueError("conv3d_mfma: skip must be a contiguous tensor of the output's shape")
+    shape = (b, 2 * d, 2 * h, 2 * w, cout) if transposed else (b, *_conv_out_dhw(d, h, w, stride), cout)
+    _layer_like("conv3d_mfma", "skip", skip, shape, x.device)
+    _layer_like("conv3d_mfma", "out", out, shape, x.device)
+    _layer_no_alias("conv3d_mfma", skip, out)
     if (cin, cout) == (8, 1):
         if tuple(w_packed.shape) != (3, 72):
             raise ValueError("conv3d_mfma: the 8 -> 1 conv takes the prob packing [3, 72] (prob_pack)")
     elif tuple(w_packed.shape) != (27, cout, cin):
         raise ValueError("conv3d_mfma: w_packed must be [27, cout, cin]")
+    y = torch.empty(shape, device=x.device) if out is None else out
     with _Span("tmvs_conv3d_mfma"):
-        _lib.check(_lib_h().tmvs_conv3d_mfma(_ptr(x.contiguous()), b, cin, d, h, w, _ptr(w_packed), cout, stride,
+        _lib.check(_lib_h().tmvs_conv3d_mfma(_ptr(x), b, cin, d, h, w, _ptr(w_packed), cout, stride,
                                              int(transposed), _ptr(skip), _ptr(y), _stream()), "tmvs_conv3d_mfma")
     return y
 
