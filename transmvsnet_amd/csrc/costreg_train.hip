@@ -22,8 +22,7 @@
 //
 // Bounds: the convolutions are fp32 FMA work (VALU; 3 x 3,456 MAC per voxel for forward + both
 // gradients), the BN passes HBM (2-3 reads of z per pass).
-#include "common.h"
-#include "reduce_mfma.h"
+#include "train_reduce.h"
 
 namespace tmvs {
 
@@ -131,7 +130,7 @@ __global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_tile_kernel(
   auto la = [&](long v, int q) { return *reinterpret_cast<const float4*>(direct + v * A + 4 * q); };
   auto lb = [&](long v, int q) {
     int b, pd, ph, pw;
-    chunk_row_coords3(v, Pd, Ph, Pw, b, pd, ph, pw);  // rows of 64-aligned chunks (wgrad_vpb: multiples of 2048)
+    chunk_row_coords3(v, Pd, Ph, Pw, b, pd, ph, pw);  // rows of 64-aligned chunks (wgrad_chunk: multiples of 2048)
     const int gd = pd * stride - 1 + kd, gh = ph * stride - 1 + kh, gw = pw * stride - 1 + kw;
     if (gd < 0 || gh < 0 || gw < 0 || gd >= Gd || gh >= Gh || gw >= Gw) return make_float4(0.f, 0.f, 0.f, 0.f);
     return *reinterpret_cast<const float4*>(gath + ((((size_t)b * Gd + gd) * Gh + gh) * Gw + gw) * BC + 4 * q);
@@ -141,22 +140,19 @@ __global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_tile_kernel(
 
 // Few (a, b) pairs, one kd plane of taps per block row (grid.y = 3): a thread reads its voxel's
 // `direct` row once per kd and the 9 neighbours' `gathered` rows (L1/L2 hits), keeping 9 x A x BC fp32
-// sums over its voxels; then per value a fixed wave butterfly (fp64) and the 4 waves in order.
+// sums over its voxels; then block_sum_store (train_reduce.h) per value.
 // Replaces 27 passes over `direct` with 3.
 template <int A, int BC>
 __global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_taps_kernel(
     const float* __restrict__ direct, const float* __restrict__ gath, int B, int Pd, int Ph, int Pw, int Gd, int Gh,
     int Gw, int stride, long vpb, double* __restrict__ partial) {
   constexpr int NPR = A * BC;
-  __shared__ double red[9 * NPR][kTrainBlock / 64];
   const int kd = blockIdx.y;
   const long nvox = (long)B * Pd * Ph * Pw;
   const long v0 = (long)blockIdx.x * vpb, v1 = v0 + vpb < nvox ? v0 + vpb : nvox;
-  float acc[9][NPR];
+  float acc[9 * NPR];  // [tap of the plane][a][b]
 #pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int q = 0; q < NPR; ++q) acc[k][q] = 0.f;
+  for (int i = 0; i < 9 * NPR; ++i) acc[i] = 0.f;
   long v = v0 + threadIdx.x;
   int pw = (int)(v % Pw), ph, pd, b;
   {
@@ -207,7 +203,7 @@ __global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_taps_kernel(
 #pragma unroll
       for (int a = 0; a < A; ++a)
 #pragma unroll
-        for (int c = 0; c < BC; ++c) acc[k][a * BC + c] = fmaf(dv[a], gv[c], acc[k][a * BC + c]);
+        for (int c = 0; c < BC; ++c) acc[(k * A + a) * BC + c] = fmaf(dv[a], gv[c], acc[(k * A + a) * BC + c]);
     }
     pw += kTrainBlock;
     while (pw >= Pw) {
@@ -221,120 +217,89 @@ __global__ __launch_bounds__(kTrainBlock) void conv3d_wgrad_taps_kernel(
       }
     }
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int q = 0; q < NPR; ++q) {
-      const double x = wave_xor_sum_dpp((double)acc[k][q]);  // the fixed xor butterfly (common.h)
-      if (lane == 0) red[k * NPR + q][wv] = x;
-    }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 9 * NPR; i += kTrainBlock)
-    partial[((size_t)blockIdx.x * 27 + kd * 9) * NPR + i] = (red[i][0] + red[i][1]) + (red[i][2] + red[i][3]);
-}
-
-// dw[i] = sum_j partial[j][i], j = 0..nblk-1 in order (fp64 accumulation)
-__global__ __launch_bounds__(kTrainBlock) void sum_partials_kernel(const double* __restrict__ partial, int nblk, long n,
-                                                                   float* __restrict__ out) {
-  // 32 outputs per block; 8 interleaved chains (partial j in chain j % 8), then the chains in order:
-  // a fixed order (bitwise reproducible) with 8x the loads in flight of one serial chain
-  __shared__ double red[8][32];
-  const int g = threadIdx.x >> 5, q = threadIdx.x & 31;
-  const long i = (long)blockIdx.x * 32 + q;
-  double s = 0.0;
-  if (i < n)
-    s = strided_sum(partial + i, g, nblk, 8, (size_t)n, s);
-  red[g][q] = s;
-  __syncthreads();
-  if (g == 0 && i < n) {
-    double t = red[0][q];
-#pragma unroll
-    for (int c = 1; c < 8; ++c) t += red[c][q];
-    out[i] = (float)t;
-  }
+  block_sum_store<true>(acc, partial + ((size_t)blockIdx.x * 27 + kd * 9) * NPR);
 }
 
 // ---------------------------------------------------------------- BatchNorm3d, train mode
-// Per-block fp64 partials of (sum z, sum z^2) per channel: thread t handles channel t % C of
-// rows t / C, t / C + 256/C, ... (C divides 256).
-// (grid.y = group: independent statistics of `groups` consecutive [nvox][C] slabs)
-__global__ __launch_bounds__(kTrainBlock) void bn_stats_partial_kernel(const float* __restrict__ z, long nvox, int C,
-                                                                       long vpb, double* __restrict__ partial) {
-  __shared__ double red[2][kTrainBlock];
-  z += (size_t)blockIdx.y * nvox * C;
-  partial += (size_t)blockIdx.y * gridDim.x * 2 * C;
-  const int c = threadIdx.x % C, r0 = threadIdx.x / C, rs = kTrainBlock / C;
-  const long v0 = (long)blockIdx.x * vpb, v1 = v0 + vpb < nvox ? v0 + vpb : nvox;
-  double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};  // 4 independent chains
-  long v = v0 + r0;
-  // groups of 4 rows, two in flight: group g+1's loads are issued before group g is accumulated
-  // (a block walks up to thousands of rows; one group at a time left each load's latency exposed);
-  // the groups are accumulated in order. (A generic ring of 2-4 groups under a rolled loop measured
-  // slower than this hand-unrolled pair, r14t.)
-  auto load4 = [&](long vv, float (&x)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] = z[(vv + (long)j * rs) * C + c];
-  };
-  auto add4 = [&](const float (&x)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s[j] += (double)x[j];
-      q[j] += (double)x[j] * (double)x[j];
-    }
-  };
-  float xa[4], xb[4];
-  if (v + 3L * rs < v1) load4(v, xa);
+// The two BatchNorm partial passes share one walk: thread t handles channel t % C of the block's rows
+// v = v0 + t / C, + rs, + 2 rs, ... (rs = 256 / C; C divides 256) and keeps two sums in 4 chains each.
+// Rows go in groups of 4 (row j of a group into chain j), two groups in flight: group g+1's loads are
+// issued before group g is accumulated (a block walks up to thousands of rows; one group at a time left
+// each load's latency exposed); the groups are accumulated in order, the rows left over one by one into
+// chain 0. Two named register sets, written out: a generic ring of 2-4 groups under a rolled loop
+// measured slower than this hand-unrolled pair (r14t).
+// load4(v, regs): rows v, v + rs, v + 2 rs, v + 3 rs into regs; add4(regs); tail(v): one row.
+template <typename Regs, typename Load4, typename Add4, typename Tail>
+__device__ __forceinline__ void walk_rows_two_groups(long v, long v1, int rs, Load4 load4, Add4 add4, Tail tail) {
+  Regs ra, rb;
+  if (v + 3L * rs < v1) load4(v, ra);
   while (v + 3L * rs < v1) {
     const long vb = v + 4L * rs;
     const bool hb = vb + 3L * rs < v1;
-    if (hb) load4(vb, xb);
-    add4(xa);
+    if (hb) load4(vb, rb);
+    add4(ra);
     v = vb;
     if (!hb) break;
     const long va = v + 4L * rs;
     const bool ha = va + 3L * rs < v1;
-    if (ha) load4(va, xa);
-    add4(xb);
+    if (ha) load4(va, ra);
+    add4(rb);
     v = va;
     if (!ha) break;
   }
-  for (; v < v1; v += rs) {
-    const double x = (double)z[v * C + c];
-    s[0] += x;
-    q[0] += x * x;
-  }
-  red[0][threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-  red[1][threadIdx.x] = (q[0] + q[1]) + (q[2] + q[3]);
+  for (; v < v1; v += rs) tail(v);
+}
+
+// ... and one end: each thread's chains as (c0 + c1) + (c2 + c3), then thread c < C adds its channel's
+// rs thread sums in thread order; partial[blockIdx.x][2][C] = (sum of a, sum of b)
+__device__ __forceinline__ void channel_pair_store(const double (&a)[4], const double (&b)[4], int C,
+                                                   double* __restrict__ partial) {
+  __shared__ double red[2][kTrainBlock];
+  red[0][threadIdx.x] = (a[0] + a[1]) + (a[2] + a[3]);
+  red[1][threadIdx.x] = (b[0] + b[1]) + (b[2] + b[3]);
   __syncthreads();
   if (threadIdx.x < C) {
-    double ts = 0.0, tq = 0.0;
-    for (int r = 0; r < rs; ++r) {
-      ts += red[0][r * C + threadIdx.x];
-      tq += red[1][r * C + threadIdx.x];
+    double ta = 0.0, tb = 0.0;
+    for (int r = 0; r < kTrainBlock / C; ++r) {
+      ta += red[0][r * C + threadIdx.x];
+      tb += red[1][r * C + threadIdx.x];
     }
-    partial[((size_t)blockIdx.x * 2 + 0) * C + threadIdx.x] = ts;
-    partial[((size_t)blockIdx.x * 2 + 1) * C + threadIdx.x] = tq;
+    partial[((size_t)blockIdx.x * 2 + 0) * C + threadIdx.x] = ta;
+    partial[((size_t)blockIdx.x * 2 + 1) * C + threadIdx.x] = tb;
   }
 }
 
-// out[k] = sum_j partial[j][k] (K values per block row): block k, threads stride j, then a fixed
-// LDS tree -- deterministic, and parallel over the (up to 4096) partial rows
-__global__ __launch_bounds__(kTrainBlock) void sum_double_partials_kernel(const double* __restrict__ partial, int nblk,
-                                                                          int K, double* __restrict__ out) {
-  __shared__ double red[kTrainBlock];
-  const int k = blockIdx.x;
-  partial += (size_t)blockIdx.y * nblk * K;  // grid.y = group
-  out += (size_t)blockIdx.y * K;
-  double a = 0.0;
-  a = strided_sum(partial + k, threadIdx.x, nblk, kTrainBlock, (size_t)K, a);
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int st = kTrainBlock / 2; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[k] = red[0];
+// Per-block fp64 partials of (sum z, sum z^2) per channel
+// (grid.y = group: independent statistics of `groups` consecutive [nvox][C] slabs)
+__global__ __launch_bounds__(kTrainBlock) void bn_stats_partial_kernel(const float* __restrict__ z, long nvox, int C,
+                                                                       long vpb, double* __restrict__ partial) {
+  z += (size_t)blockIdx.y * nvox * C;
+  partial += (size_t)blockIdx.y * gridDim.x * 2 * C;
+  const int c = threadIdx.x % C, r0 = threadIdx.x / C, rs = kTrainBlock / C;
+  const long v0 = (long)blockIdx.x * vpb, v1 = v0 + vpb < nvox ? v0 + vpb : nvox;
+  double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+  struct Regs {
+    float x[4];
+  };
+  walk_rows_two_groups<Regs>(
+      v0 + r0, v1, rs,
+      [&](long vv, Regs& r) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r.x[j] = z[(vv + (long)j * rs) * C + c];
+      },
+      [&](const Regs& r) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          s[j] += (double)r.x[j];
+          q[j] += (double)r.x[j] * (double)r.x[j];
+        }
+      },
+      [&](long v) {
+        const double x = (double)z[v * C + c];
+        s[0] += x;
+        q[0] += x * x;
+      });
+  channel_pair_store(s, q, C, partial);
 }
 
 // mean, biased var (fp32) from the summed (sum z, sum z^2)
@@ -345,24 +310,18 @@ __device__ __forceinline__ void bn_stats_from_sums(double s, double s2, long nvo
   var = (float)(v > 0.0 ? v : 0.0);
 }
 
-// sum_double_partials_kernel's two sums of channel c (sum z, sum z^2; the same thread strides and LDS
-// tree) and bn_stats_from_sums in one launch: grid (C, groups)
+// sum_partials_f64_kernel's two sums of channel c (sum z, sum z^2: tree_sum_256, train_reduce.h) and
+// bn_stats_from_sums in one launch: grid (C, groups)
 __global__ __launch_bounds__(kTrainBlock) void bn_sums_stats_kernel(const double* __restrict__ partial, int nblk, int C,
                                                                     long nvox, float* __restrict__ mean,
                                                                     float* __restrict__ var) {
-  __shared__ double red[kTrainBlock];
   __shared__ double tot[2];
   const int c = blockIdx.x, K = 2 * C;
   partial += (size_t)blockIdx.y * nblk * K;
 #pragma unroll 1
   for (int h = 0; h < 2; ++h) {
-    red[threadIdx.x] = strided_sum(partial + h * C + c, threadIdx.x, nblk, kTrainBlock, (size_t)K, 0.0);
-    __syncthreads();
-    for (int st = kTrainBlock / 2; st > 0; st >>= 1) {
-      if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) tot[h] = red[0];
+    const double t = tree_sum_256(partial + h * C + c, nblk, (size_t)K);
+    if (threadIdx.x == 0) tot[h] = t;
     __syncthreads();
   }
   if (threadIdx.x == 0)
@@ -374,57 +333,58 @@ __device__ __forceinline__ void bn_affine(float mean, float var, float g, float 
   sh = fmaf(-mean, al, bt);
 }
 
-// out = relu(fmaf(z, alpha, shift)) [+ skip]; group i / per uses statistics [group][C]
-__global__ __launch_bounds__(kTrainBlock) void bn_relu_apply_kernel(const float* __restrict__ z, long n, long per, int C,
-                                                                    const float* __restrict__ mean,
+// VEC consecutive floats as one load / store: VEC = 4 moves a 16-byte-aligned quad
+template <int VEC>
+__device__ __forceinline__ void load_vec(const float* __restrict__ p, float (&v)[VEC]) {
+  static_assert(VEC == 1 || VEC == 4, "scalar or float4");
+  if constexpr (VEC == 4) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    v[0] = t.x;
+    v[1] = t.y;
+    v[2] = t.z;
+    v[3] = t.w;
+  } else {
+    v[0] = *p;
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void store_vec(float* __restrict__ p, const float (&v)[VEC]) {
+  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else *p = v[0];
+}
+
+// out = relu(fmaf(z, alpha, shift)) [+ skip]; group i / per uses statistics [group][C]. A thread takes
+// VEC consecutive elements (nv = n / VEC threads). VEC = 4 (C % 4 == 0, 16-byte aligned tensors): the
+// channel / group indices once per 4 elements instead of a 64-bit divide per element; one body per
+// element for both, so the same bits.
+template <int VEC>
+__global__ __launch_bounds__(kTrainBlock) void bn_relu_apply_kernel(const float* __restrict__ z, long nv, long per,
+                                                                    int C, const float* __restrict__ mean,
                                                                     const float* __restrict__ var,
                                                                     const float* __restrict__ gamma,
                                                                     const float* __restrict__ beta, float eps,
                                                                     const float* __restrict__ skip,
                                                                     float* __restrict__ out) {
-  const long i = (long)blockIdx.x * kTrainBlock + threadIdx.x;
-  if (i >= n) return;
-  const int c = (int)(i % C);
-  const long gc = (i / per) * C + c;
-  float al, sh;
-  bn_affine(mean[gc], var[gc], gamma[c], beta[c], eps, al, sh);
-  float y = relu(fmaf(z[i], al, sh));
-  if (skip) y = skip[i] + y;
-  out[i] = y;
-}
-
-// bn_relu_apply_kernel on float4s (C % 4 == 0, 16-byte aligned tensors): the channel / group indices
-// and the per-channel affine once per 4 elements instead of a 64-bit divide and a sqrt per element;
-// the same arithmetic per element, so the same bits
-__global__ __launch_bounds__(kTrainBlock) void bn_relu_apply4_kernel(const float4* __restrict__ z, long n4, long per,
-                                                                     int C, const float* __restrict__ mean,
-                                                                     const float* __restrict__ var,
-                                                                     const float* __restrict__ gamma,
-                                                                     const float* __restrict__ beta, float eps,
-                                                                     const float4* __restrict__ skip,
-                                                                     float4* __restrict__ out) {
-  const long i4 = (long)blockIdx.x * kTrainBlock + threadIdx.x;
-  if (i4 >= n4) return;
-  const long i = 4 * i4;
+  const long iv = (long)blockIdx.x * kTrainBlock + threadIdx.x;
+  if (iv >= nv) return;
+  const long i = VEC * iv;
   const int c0 = (int)(i % C);
   const long g0 = (i / per) * C + c0;
-  const float4 zv = z[i4];
-  const float zz[4] = {zv.x, zv.y, zv.z, zv.w};
-  float y[4];
+  float zz[VEC], y[VEC];
+  load_vec<VEC>(z + i, zz);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < VEC; ++j) {
     float al, sh;
     bn_affine(mean[g0 + j], var[g0 + j], gamma[c0 + j], beta[c0 + j], eps, al, sh);
     y[j] = relu(fmaf(zz[j], al, sh));
   }
   if (skip) {
-    const float4 sv = skip[i4];
-    y[0] = sv.x + y[0];
-    y[1] = sv.y + y[1];
-    y[2] = sv.z + y[2];
-    y[3] = sv.w + y[3];
+    float sv[VEC];
+    load_vec<VEC>(skip + i, sv);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) y[j] = sv[j] + y[j];
   }
-  out[i4] = make_float4(y[0], y[1], y[2], y[3]);
+  store_vec<VEC>(out + i, y);
 }
 
 // backward pass 1: per-block fp64 partials of (sum g, sum g*xhat), g = dy * [fmaf(z, alpha, shift) > 0]
@@ -432,7 +392,6 @@ __global__ __launch_bounds__(kTrainBlock) void bn_relu_bwd_partial_kernel(
     const float* __restrict__ dy, const float* __restrict__ z, long nvox, int C, const float* __restrict__ mean,
     const float* __restrict__ var, const float* __restrict__ gamma, const float* __restrict__ beta, float eps, long vpb,
     double* __restrict__ partial) {
-  __shared__ double red[2][kTrainBlock];
   const int c = threadIdx.x % C, r0 = threadIdx.x / C, rs = kTrainBlock / C;
   dy += (size_t)blockIdx.y * nvox * C;  // grid.y = group
   z += (size_t)blockIdx.y * nvox * C;
@@ -444,57 +403,29 @@ __global__ __launch_bounds__(kTrainBlock) void bn_relu_bwd_partial_kernel(
   const float m = mean[c], rstd = 1.f / sqrtf(var[c] + eps);
   const long v0 = (long)blockIdx.x * vpb, v1 = v0 + vpb < nvox ? v0 + vpb : nvox;
   double sg[4] = {0.0, 0.0, 0.0, 0.0}, sgx[4] = {0.0, 0.0, 0.0, 0.0};
-  long v = v0 + r0;
-  // groups of 4 rows, two in flight (as bn_stats_partial_kernel), accumulated in the same order
-  auto load4 = [&](long vv, float (&zz)[4], float (&gg)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      zz[j] = z[(vv + (long)j * rs) * C + c];
-      gg[j] = dy[(vv + (long)j * rs) * C + c];
-    }
+  auto add1 = [&](float zz, float gg, int j) {
+    const float g = fmaf(zz, al, sh) > 0.f ? gg : 0.f;
+    sg[j] += (double)g;
+    sgx[j] += (double)g * (double)((zz - m) * rstd);
   };
-  auto add4 = [&](const float (&zz)[4], const float (&gg)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float g = fmaf(zz[j], al, sh) > 0.f ? gg[j] : 0.f;
-      sg[j] += (double)g;
-      sgx[j] += (double)g * (double)((zz[j] - m) * rstd);
-    }
+  struct Regs {
+    float z[4], g[4];
   };
-  float za[4], ga[4], zb[4], gb[4];
-  if (v + 3L * rs < v1) load4(v, za, ga);
-  while (v + 3L * rs < v1) {
-    const long vb = v + 4L * rs;
-    const bool hb = vb + 3L * rs < v1;
-    if (hb) load4(vb, zb, gb);
-    add4(za, ga);
-    v = vb;
-    if (!hb) break;
-    const long va = v + 4L * rs;
-    const bool ha = va + 3L * rs < v1;
-    if (ha) load4(va, za, ga);
-    add4(zb, gb);
-    v = va;
-    if (!ha) break;
-  }
-  for (; v < v1; v += rs) {
-    const float zz = z[v * C + c];
-    const float g = fmaf(zz, al, sh) > 0.f ? dy[v * C + c] : 0.f;
-    sg[0] += (double)g;
-    sgx[0] += (double)g * (double)((zz - m) * rstd);
-  }
-  red[0][threadIdx.x] = (sg[0] + sg[1]) + (sg[2] + sg[3]);
-  red[1][threadIdx.x] = (sgx[0] + sgx[1]) + (sgx[2] + sgx[3]);
-  __syncthreads();
-  if (threadIdx.x < C) {
-    double a = 0.0, b = 0.0;
-    for (int r = 0; r < rs; ++r) {
-      a += red[0][r * C + threadIdx.x];
-      b += red[1][r * C + threadIdx.x];
-    }
-    partial[((size_t)blockIdx.x * 2 + 0) * C + threadIdx.x] = a;
-    partial[((size_t)blockIdx.x * 2 + 1) * C + threadIdx.x] = b;
-  }
+  walk_rows_two_groups<Regs>(
+      v0 + r0, v1, rs,
+      [&](long vv, Regs& r) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          r.z[j] = z[(vv + (long)j * rs) * C + c];
+          r.g[j] = dy[(vv + (long)j * rs) * C + c];
+        }
+      },
+      [&](const Regs& r) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) add1(r.z[j], r.g[j], j);
+      },
+      [&](long v) { add1(z[v * C + c], dy[v * C + c], 0); });
+  channel_pair_store(sg, sgx, C, partial);
 }
 
 // dbeta = sum g, dgamma = sum g*xhat from the summed partials: per group in fp32, then added over the
@@ -513,50 +444,28 @@ __device__ __forceinline__ void bn_relu_bwd_finalize(const double* __restrict__ 
   dgamma[c] = g;
 }
 
-// pass 2: dz = gamma*rstd/N * (N*g - sum g - xhat * sum g*xhat)
+// pass 2: dz = gamma*rstd/N * (N*g - sum g - xhat * sum g*xhat); VEC elements per thread as
+// bn_relu_apply_kernel (one body per element, the same bits)
+template <int VEC>
 __global__ __launch_bounds__(kTrainBlock) void bn_relu_bwd_apply_kernel(
-    const float* __restrict__ dy, const float* __restrict__ z, long n, int C, long nvox, const float* __restrict__ mean,
+    const float* __restrict__ dy, const float* __restrict__ z, long nv, int C, long nvox, const float* __restrict__ mean,
     const float* __restrict__ var, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
     const double* __restrict__ sums, int groups, float* __restrict__ dgamma, float* __restrict__ dbeta,
     float* __restrict__ dz) {
   bn_relu_bwd_finalize(sums, C, groups, dgamma, dbeta);
-  const long i = (long)blockIdx.x * kTrainBlock + threadIdx.x;
-  if (i >= n) return;
-  const int c = (int)(i % C);
-  const long grp = i / (nvox * C);  // statistics and sums of element i's group
-  const long gc = grp * C + c;
-  const double* sg = sums + (size_t)grp * 2 * C;
-  float al, sh;
-  bn_affine(mean[gc], var[gc], gamma[c], beta[c], eps, al, sh);
-  const float zz = z[i];
-  const float rstd = 1.f / sqrtf(var[gc] + eps);
-  const float xhat = (zz - mean[gc]) * rstd;
-  const float g = fmaf(zz, al, sh) > 0.f ? dy[i] : 0.f;
-  const double inv_n = 1.0 / (double)nvox;
-  const float mg = (float)(sg[c] * inv_n), mgx = (float)(sg[C + c] * inv_n);
-  dz[i] = (gamma[c] * rstd) * ((g - mg) - xhat * mgx);
-}
-
-// bn_relu_bwd_apply_kernel on float4s (C % 4 == 0, 16-byte aligned): same per-element arithmetic
-__global__ __launch_bounds__(kTrainBlock) void bn_relu_bwd_apply4_kernel(
-    const float4* __restrict__ dy, const float4* __restrict__ z, long n4, int C, long nvox,
-    const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float eps, const double* __restrict__ sums, int groups, float* __restrict__ dgamma,
-    float* __restrict__ dbeta, float4* __restrict__ dz) {
-  bn_relu_bwd_finalize(sums, C, groups, dgamma, dbeta);
-  const long i4 = (long)blockIdx.x * kTrainBlock + threadIdx.x;
-  if (i4 >= n4) return;
-  const long i = 4 * i4;
+  const long iv = (long)blockIdx.x * kTrainBlock + threadIdx.x;
+  if (iv >= nv) return;
+  const long i = VEC * iv;
   const int c0 = (int)(i % C);
-  const long grp = i / (nvox * C);
+  const long grp = i / (nvox * C);  // statistics and sums of element i's group
   const long g0 = grp * C + c0;
   const double* sg = sums + (size_t)grp * 2 * C;
+  float zz[VEC], dd[VEC], o[VEC];
+  load_vec<VEC>(z + i, zz);
+  load_vec<VEC>(dy + i, dd);
   const double inv_n = 1.0 / (double)nvox;
-  const float4 zv = z[i4], dv = dy[i4];
-  const float zz[4] = {zv.x, zv.y, zv.z, zv.w}, dd[4] = {dv.x, dv.y, dv.z, dv.w};
-  float o[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < VEC; ++j) {
     const int c = c0 + j;
     const long gc = g0 + j;
     float al, sh;
@@ -567,10 +476,8 @@ __global__ __launch_bounds__(kTrainBlock) void bn_relu_bwd_apply4_kernel(
     const float mg = (float)(sg[c] * inv_n), mgx = (float)(sg[C + c] * inv_n);
     o[j] = (gamma[c] * rstd) * ((g - mg) - xhat * mgx);
   }
-  dz[i4] = make_float4(o[0], o[1], o[2], o[3]);
+  store_vec<VEC>(dz + i, o);
 }
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---------------------------------------------------------------- dispatch helpers
 template <int CIN, int COB>
@@ -584,18 +491,15 @@ static int launch_generic(const float* x, const float* w, int cout, int B, int D
   return TMVS_OK;
 }
 
-static long wgrad_vpb(long nvox) {
-  long vpb = 2048;
-  while ((nvox + vpb - 1) / vpb > 512) vpb *= 2;
-  return vpb;
-}
+// voxel ranges of the partial passes (chunk_for, train_reduce.h)
+static Chunk wgrad_chunk(long nvox) { return chunk_for(nvox, 2048, 512); }
+static Chunk bn_chunk(long nvox) { return chunk_for(nvox, 1024, 4096); }
 
 template <int A, int BC>
 static int launch_wgrad(const float* direct, const float* gath, int B, int Pd, int Ph, int Pw, int Gd, int Gh, int Gw,
                         int stride, double* ws, float* dw, hipStream_t st) {
   const long nvox = (long)B * Pd * Ph * Pw;
-  const long vpb = wgrad_vpb(nvox);
-  const int nblk = (int)((nvox + vpb - 1) / vpb);
+  const auto [vpb, nblk] = wgrad_chunk(nvox);
   // the taps kernel for the few-pair layers (conv0: 8 x 1, prob: 1 x 8), the matrix-core tile otherwise
   static_assert(A * BC <= 8 || (A % 8 == 0 && BC % 8 == 0), "no weight-gradient kernel for this channel pair");
   if constexpr (A * BC <= 8)
@@ -605,20 +509,12 @@ static int launch_wgrad(const float* direct, const float* gath, int B, int Pd, i
     hipLaunchKernelGGL((conv3d_wgrad_tile_kernel<A, BC>), xcd_range_tap_grid(27, nblk), dim3(kTrainBlock), 0, st, direct,
                        gath, B, Pd, Ph, Pw, Gd, Gh, Gw, stride, vpb, nblk, ws);
   TMVS_CHECK_LAUNCH();
-  const long n = 27L * A * BC;
-  hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((n + 31) / 32)), dim3(kTrainBlock), 0,
-                     st, ws, nblk, n, dw);
+  sum_partials_f32(ws, nblk, 27L * A * BC, dw, st);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }
 
 static bool valid_ch(int c) { return c == 1 || c == 8 || c == 16 || c == 32 || c == 64; }
-
-static long bn_vpb(long nvox) {
-  long vpb = 1024;
-  while ((nvox + vpb - 1) / vpb > 4096) vpb *= 2;
-  return vpb;
-}
 
 }  // namespace tmvs
 
@@ -659,8 +555,7 @@ extern "C" int tmvs_conv3d_generic(const float* x, int batch, int cin, int d_in,
 
 extern "C" size_t tmvs_conv3d_wgrad_workspace(int batch, int d, int h, int w, int a_ch, int b_ch) {
   const long nvox = (long)batch * d * h * w;
-  const long vpb = wgrad_vpb(nvox);
-  return (size_t)((nvox + vpb - 1) / vpb) * 27 * a_ch * b_ch * sizeof(double);
+  return (size_t)wgrad_chunk(nvox).blocks * 27 * a_ch * b_ch * sizeof(double);
 }
 
 extern "C" int tmvs_conv3d_wgrad(const float* direct, int a_ch, int batch, int pd, int ph, int pw, const float* gathered,
@@ -684,8 +579,7 @@ extern "C" int tmvs_conv3d_wgrad(const float* direct, int a_ch, int batch, int p
 }
 
 static size_t bn_group_ws(long nvox, int channels) {
-  const long vpb = bn_vpb(nvox);
-  return (size_t)((nvox + vpb - 1) / vpb) * 2 * channels * sizeof(double) + 2 * channels * sizeof(double);
+  return (size_t)bn_chunk(nvox).blocks * 2 * channels * sizeof(double) + 2 * channels * sizeof(double);
 }
 
 extern "C" size_t tmvs_bn_train_workspace(long nvox, int channels) { return bn_group_ws(nvox, channels); }
@@ -700,8 +594,7 @@ extern "C" int tmvs_bn_stats_grouped(const float* z, int groups, long nvox, int 
   if (channels <= 0 || kTrainBlock % channels) return TMVS_ERR_SHAPE;
   if (workspace_bytes < tmvs_bn_train_workspace_grouped(groups, nvox, channels)) return TMVS_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const long vpb = bn_vpb(nvox);
-  const int nblk = (int)((nvox + vpb - 1) / vpb);
+  const auto [vpb, nblk] = bn_chunk(nvox);
   double* part = (double*)workspace;
   hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nblk, groups), dim3(kTrainBlock), 0, st, z, nvox, channels, vpb,
                      part);
@@ -725,13 +618,13 @@ extern "C" int tmvs_bn_relu_train_grouped(const float* z, int groups, long nvox,
   if (kTrainBlock % channels) return TMVS_ERR_SHAPE;  // as the statistics and the backward: C divides 256
   const long per = nvox * channels, n = per * groups;
   if (channels % 4 == 0 && aligned16(z) && aligned16(out) && (!skip || aligned16(skip))) {
-    const long n4 = n / 4;
-    hipLaunchKernelGGL(bn_relu_apply4_kernel, dim3((unsigned)((n4 + kTrainBlock - 1) / kTrainBlock)), dim3(kTrainBlock),
-                       0, (hipStream_t)stream, (const float4*)z, n4, per, channels, mean, var, gamma, beta, eps,
-                       (const float4*)skip, (float4*)out);
+    hipLaunchKernelGGL(bn_relu_apply_kernel<4>, dim3((unsigned)((n / 4 + kTrainBlock - 1) / kTrainBlock)),
+                       dim3(kTrainBlock), 0, (hipStream_t)stream, z, n / 4, per, channels, mean, var, gamma, beta, eps,
+                       skip, out);
   } else {
-    hipLaunchKernelGGL(bn_relu_apply_kernel, dim3((unsigned)((n + kTrainBlock - 1) / kTrainBlock)), dim3(kTrainBlock),
-                       0, (hipStream_t)stream, z, n, per, channels, mean, var, gamma, beta, eps, skip, out);
+    hipLaunchKernelGGL(bn_relu_apply_kernel<1>, dim3((unsigned)((n + kTrainBlock - 1) / kTrainBlock)),
+                       dim3(kTrainBlock), 0, (hipStream_t)stream, z, n, per, channels, mean, var, gamma, beta, eps, skip,
+                       out);
   }
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
@@ -753,24 +646,22 @@ extern "C" int tmvs_bn_relu_backward_grouped(const float* dy, const float* z, in
   if (channels <= 0 || kTrainBlock % channels) return TMVS_ERR_SHAPE;
   if (workspace_bytes < tmvs_bn_train_workspace_grouped(groups, nvox, channels)) return TMVS_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const long vpb = bn_vpb(nvox);
-  const int nblk = (int)((nvox + vpb - 1) / vpb);
+  const auto [vpb, nblk] = bn_chunk(nvox);
   double* part = (double*)workspace;
   double* sums = part + (size_t)groups * nblk * 2 * channels;
   hipLaunchKernelGGL(bn_relu_bwd_partial_kernel, dim3(nblk, groups), dim3(kTrainBlock), 0, st, dy, z, nvox, channels,
                      mean, var, gamma, beta, eps, vpb, part);
   TMVS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sum_double_partials_kernel, dim3(2 * channels, groups), dim3(kTrainBlock), 0, st,
+  hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(2 * channels, groups), dim3(kTrainBlock), 0, st,
                      (const double*)part, nblk, 2 * channels, sums);
   TMVS_CHECK_LAUNCH();
   const long n = nvox * channels * groups;
   if (channels % 4 == 0 && aligned16(dy) && aligned16(z) && aligned16(dz)) {
-    const long n4 = n / 4;
-    hipLaunchKernelGGL(bn_relu_bwd_apply4_kernel, dim3((unsigned)((n4 + kTrainBlock - 1) / kTrainBlock)),
-                       dim3(kTrainBlock), 0, st, (const float4*)dy, (const float4*)z, n4, channels, nvox, mean, var,
-                       gamma, beta, eps, (const double*)sums, groups, dgamma, dbeta, (float4*)dz);
+    hipLaunchKernelGGL(bn_relu_bwd_apply_kernel<4>, dim3((unsigned)((n / 4 + kTrainBlock - 1) / kTrainBlock)),
+                       dim3(kTrainBlock), 0, st, dy, z, n / 4, channels, nvox, mean, var, gamma, beta, eps,
+                       (const double*)sums, groups, dgamma, dbeta, dz);
   } else {
-    hipLaunchKernelGGL(bn_relu_bwd_apply_kernel, dim3((unsigned)((n + kTrainBlock - 1) / kTrainBlock)),
+    hipLaunchKernelGGL(bn_relu_bwd_apply_kernel<1>, dim3((unsigned)((n + kTrainBlock - 1) / kTrainBlock)),
                        dim3(kTrainBlock), 0, st, dy, z, n, channels, nvox, mean, var, gamma, beta, eps,
                        (const double*)sums, groups, dgamma, dbeta, dz);
   }

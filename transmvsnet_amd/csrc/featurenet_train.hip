@@ -26,8 +26,7 @@
 // cycles per wave-instruction per CU, scripts/micro/lds_atomic.hip) -- converted once and summed per
 // texel in a fixed block order; only corners beyond the window (offsets over R px) go to global
 // memory with fp32 atomics, as torchvision's deformable_col2im adds every contribution with atomicAdd.
-#include "common.h"
-#include "reduce_mfma.h"
+#include "train_reduce.h"
 
 namespace tmvs {
 namespace {
@@ -220,7 +219,7 @@ __global__ __launch_bounds__(kBlk) void conv2d_wgrad_kernel(const float* __restr
   auto la = [&](long v, int q) { return load_row4(direct, v, a_ch, q); };
   auto lb = [&](long v, int q) {
     int b, ph, pw;
-    chunk_row_coords(v, Ph, Pw, b, ph, pw);  // rows of 64-aligned chunks (ppb_for: multiples of 1024)
+    chunk_row_coords(v, Ph, Pw, b, ph, pw);  // rows of 64-aligned chunks (wgrad_chunk: multiples of 1024)
     const int gh = ph * stride - pad + kh, gw = pw * stride - pad + kw;
     if (gh < 0 || gw < 0 || gh >= Gh || gw >= Gw) return make_float4(0.f, 0.f, 0.f, 0.f);
     return *reinterpret_cast<const float4*>(gath + (((size_t)b * Gh + gh) * Gw + gw) * BC + 4 * q);
@@ -236,7 +235,6 @@ __global__ __launch_bounds__(kBlk) void conv2d_wgrad_small_kernel(const float* _
                                                                  int Gh, int Gw, int K, int stride, int pad, long ppb,
                                                                  int nblk, double* __restrict__ partial) {
   constexpr int NPR = A * BC;
-  __shared__ double red[NPR][kBlk / 64];
   int rb, k;
   if (!xcd_range_tap(K * K, nblk, rb, k)) return;
   const int kh = k / K, kw = k % K;
@@ -262,74 +260,17 @@ __global__ __launch_bounds__(kBlk) void conv2d_wgrad_small_kernel(const float* _
       for (int c = 0; c < BC; ++c) acc[a * BC + c] = fmaf(d, gv[c], acc[a * BC + c]);
     }
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < NPR; ++q) {
-    const double x = wave_xor_sum_dpp((double)acc[q]);  // the fixed xor butterfly (common.h)
-    if (lane == 0) red[q][wv] = x;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < NPR; i += kBlk)
-    partial[((size_t)rb * K * K + k) * NPR + i] = (red[i][0] + red[i][1]) + (red[i][2] + red[i][3]);
+  block_sum_store<true>(acc, partial + ((size_t)rb * K * K + k) * NPR);
 }
 
-// out[i] = sum_j partial[j][i] in a fixed order (8 interleaved chains, then the chains in order)
-__global__ __launch_bounds__(kBlk) void sum_partials_f32_kernel(const double* __restrict__ partial, int nblk, long n,
-                                                                float* __restrict__ out) {
-  __shared__ double red[8][32];
-  const int g = threadIdx.x >> 5, q = threadIdx.x & 31;
-  const long i = (long)blockIdx.x * 32 + q;
-  double s = 0.0;
-  if (i < n)
-    s = strided_sum(partial + i, g, nblk, 8, (size_t)n, s);
-  red[g][q] = s;
-  __syncthreads();
-  if (g == 0 && i < n) {
-    double t = red[0][q];
-#pragma unroll
-    for (int c = 1; c < 8; ++c) t += red[c][q];
-    out[i] = (float)t;
-  }
-}
-
-// the same with [nblk][taps][ap][b] partials (rows padded to ap) -> dw [taps][a][b]
-__global__ __launch_bounds__(kBlk) void sum_partials_rows_kernel(const double* __restrict__ partial, int nblk, int ap,
-                                                                 int a, int bc, long n, float* __restrict__ out) {
-  __shared__ double red[8][32];
-  const int g = threadIdx.x >> 5, q = threadIdx.x & 31;
-  const long i = (long)blockIdx.x * 32 + q;
-  const long per = (long)a * bc;
-  const long src = i < n ? ((i / per) * ap + (i % per) / bc) * bc + i % bc : 0;
-  const long np = n / per * ap * bc;
-  double s = 0.0;
-  if (i < n)
-    s = strided_sum(partial + src, g, nblk, 8, (size_t)np, s);
-  red[g][q] = s;
-  __syncthreads();
-  if (g == 0 && i < n) {
-    double t = red[0][q];
-#pragma unroll
-    for (int c = 1; c < 8; ++c) t += red[c][q];
-    out[i] = (float)t;
-  }
-}
-
-// per-block fp64 partial column sums of x [n][C] (C <= 32): thread (r, c) = (t / 32, t % 32)
+// per-block fp64 partial column sums of x [n][C] (C <= 32): the block's rows in chain_sum's 8 chains
+// (train_reduce.h), column c = t % 32
 __global__ __launch_bounds__(kBlk) void colsum_partial_kernel(const float* __restrict__ x, long n, int C, long ppb,
                                                               double* __restrict__ partial) {
-  __shared__ double red[8][32];
-  const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+  const int c = threadIdx.x & 31;
   const long v0 = (long)blockIdx.x * ppb, v1 = v0 + ppb < n ? v0 + ppb : n;
-  double s = 0.0;
-  if (c < C) s = strided_sum(x + c, v0 + r0, v1, 8, (size_t)C, s);
-  red[r0][c] = s;
-  __syncthreads();
-  if (r0 == 0 && c < C) {
-    double t = red[0][c];
-#pragma unroll
-    for (int r = 1; r < 8; ++r) t += red[r][c];
-    partial[(size_t)blockIdx.x * C + c] = t;
-  }
+  double t;
+  if (chain_sum<8>(x + v0 * C + c, c < C, v1 - v0, (size_t)C, t)) partial[(size_t)blockIdx.x * C + c] = t;
 }
 
 // ---------------------------------------------------------------- DCN backward
@@ -716,7 +657,7 @@ __global__ __launch_bounds__(kBlk) void dcn_bwd_weight_kernel(const float* __res
   };
   auto sample_at = [&](long v, int& b) {
     int yy, xx;
-    chunk_row_coords(v, H, W, b, yy, xx);  // rows of 64-aligned chunks (ppb_for: multiples of 1024)
+    chunk_row_coords(v, H, W, b, yy, xx);  // rows of 64-aligned chunks (wgrad_chunk: multiples of 1024)
     const long p = (long)yy * W + xx;
     return dcn_sample(om + (size_t)b * 27 * HW + p, (size_t)HW, yy, xx, k, H, W);
   };
@@ -764,11 +705,9 @@ __global__ __launch_bounds__(kBlk) void softmax_bwd_kernel(const float* __restri
   for (int d = 0; d < D; ++d) op[(size_t)d * HW] = pp[(size_t)d * HW] * (gp[(size_t)d * HW] - s);
 }
 
-long ppb_for(long n, int max_blocks) {
-  long ppb = 1024;
-  while ((n + ppb - 1) / ppb > max_blocks) ppb *= 2;
-  return ppb;
-}
+// pixel ranges of the partial passes (chunk_for, train_reduce.h)
+Chunk wgrad_chunk(long np) { return chunk_for(np, 1024, 512); }  // conv2d and DCN weight gradients
+Chunk colsum_chunk(long n) { return chunk_for(n, 1024, 1024); }
 
 }  // namespace
 }  // namespace tmvs
@@ -804,8 +743,7 @@ static int wgrad_ap(int a) { return (a + 7) / 8 * 8; }
 
 extern "C" size_t tmvs_conv2d_wgrad_workspace(int batch, int h, int w, int a_ch, int b_ch, int k) {
   const long np = (long)batch * h * w;
-  const long ppb = ppb_for(np, 512);
-  return (size_t)((np + ppb - 1) / ppb) * k * k * wgrad_ap(a_ch) * b_ch * sizeof(double);
+  return (size_t)wgrad_chunk(np).blocks * k * k * wgrad_ap(a_ch) * b_ch * sizeof(double);
 }
 
 // dw [k*k][a_ch][b_ch]
@@ -818,8 +756,7 @@ extern "C" int tmvs_conv2d_wgrad(const float* direct, int a_ch, int batch, int p
   if (workspace_bytes < tmvs_conv2d_wgrad_workspace(batch, ph, pw, a_ch, b_ch, k)) return TMVS_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const long np = (long)batch * ph * pw;
-  const long ppb = ppb_for(np, 512);
-  const int nblk = (int)((np + ppb - 1) / ppb);
+  const auto [ppb, nblk] = wgrad_chunk(np);
   double* part = (double*)workspace;
   int ap = wgrad_ap(a_ch);
   bool done = false;
@@ -841,16 +778,13 @@ extern "C" int tmvs_conv2d_wgrad(const float* direct, int a_ch, int batch, int p
   if (!done) return TMVS_ERR_SHAPE;
   TMVS_CHECK_LAUNCH();
   // combine [nblk][k*k][ap][b] -> [k*k][a][b] (rows >= a_ch are padding)
-  const long n = (long)k * k * a_ch * b_ch;
-  hipLaunchKernelGGL(sum_partials_rows_kernel, dim3((unsigned)((n + 31) / 32)), dim3(kBlk), 0, st, (const double*)part,
-                     nblk, ap, a_ch, b_ch, n, dw);
+  sum_partials_f32<true>(part, nblk, (long)k * k * a_ch * b_ch, dw, st, ap, a_ch, b_ch);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }
 
 extern "C" size_t tmvs_colsum_workspace(long n, int channels) {
-  const long ppb = ppb_for(n, 1024);
-  return (size_t)((n + ppb - 1) / ppb) * channels * sizeof(double);
+  return (size_t)colsum_chunk(n).blocks * channels * sizeof(double);
 }
 
 extern "C" int tmvs_colsum(const float* x, long n, int channels, void* workspace, size_t workspace_bytes, float* out,
@@ -858,21 +792,18 @@ extern "C" int tmvs_colsum(const float* x, long n, int channels, void* workspace
   if (!x || !workspace || !out || n <= 0 || channels <= 0 || channels > 32) return TMVS_ERR_ARG;
   if (workspace_bytes < tmvs_colsum_workspace(n, channels)) return TMVS_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const long ppb = ppb_for(n, 1024);
-  const int nblk = (int)((n + ppb - 1) / ppb);
+  const auto [ppb, nblk] = colsum_chunk(n);
   double* part = (double*)workspace;
   hipLaunchKernelGGL(colsum_partial_kernel, dim3(nblk), dim3(kBlk), 0, st, x, n, channels, ppb, part);
   TMVS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sum_partials_f32_kernel, dim3((unsigned)((channels + 31) / 32)), dim3(kBlk), 0, st,
-                     (const double*)part, nblk, (long)channels, out);
+  sum_partials_f32(part, nblk, channels, out, st);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }
 
 static size_t dcn_partials_bytes(int batch, int cout, int height, int width) {
   const long np = (long)batch * height * width;
-  const long ppb = ppb_for(np, 512);
-  return ((size_t)((np + ppb - 1) / ppb) * 9 * cout * 32 * sizeof(double) + 255) & ~(size_t)255;
+  return ((size_t)wgrad_chunk(np).blocks * 9 * cout * 32 * sizeof(double) + 255) & ~(size_t)255;
 }
 
 static long dcn_data_blocks(int batch, int height, int width) {
@@ -900,8 +831,7 @@ static int dcn_backward_impl(const float* x_nhwc, const float* offset_mask, cons
   hipStream_t st = (hipStream_t)stream;
   const unsigned nbd = (unsigned)dcn_data_blocks(batch, height, width);
   const long np = (long)batch * height * width;
-  const long ppb = ppb_for(np, 512);
-  const int nblk = (int)((np + ppb - 1) / ppb);
+  const auto [ppb, nblk] = wgrad_chunk(np);
   double* part = (double*)workspace;
   float* scratch = (float*)((char*)workspace + dcn_partials_bytes(batch, cout, height, width));
   unsigned* absmax = (unsigned*)((char*)scratch + dcn_scratch_bytes(batch, height, width));
@@ -929,9 +859,7 @@ static int dcn_backward_impl(const float* x_nhwc, const float* offset_mask, cons
   }
 #undef TMVS_DCNB
   TMVS_CHECK_LAUNCH();
-  const long n = 9L * cout * 32;
-  hipLaunchKernelGGL(sum_partials_f32_kernel, dim3((unsigned)((n + 31) / 32)), dim3(kBlk), 0, st, (const double*)part,
-                     nblk, n, dw_taps);
+  sum_partials_f32(part, nblk, 9L * cout * 32, dw_taps, st);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }

@@ -11,7 +11,7 @@
 //   tmvs_linattn_bwd_kv    dk (through the elu), dv of the source tokens
 // KV layout as the forward (csrc/fmt.hip): kv[h*16 + m*4 + d] = sum_s K[s,h,d] V[s,h,m], Ksum at
 // 128 + h*4 + d. fp32 per token, fp64 in every cross-token reduction, no atomics.
-#include "common.h"
+#include "train_reduce.h"
 
 namespace tmvs {
 
@@ -205,23 +205,14 @@ __global__ __launch_bounds__(kTB) void token_wgrad_kernel(const float* __restric
   }
 }
 
-// out0[i] (i < n0) / out1[i - n0] = sum over the block partials: 16 interleaved chains (block j in chain
-// j % 16), then the 16 chain sums in order -- a fixed order, bitwise reproducible
+// out0[i] (i < n0) / out1[i - n0] = sum over the block partials (chain_sum, train_reduce.h: 16 chains x 16
+// values per block), set or accumulated
 __global__ __launch_bounds__(kTB) void fmt_sum_partials_kernel(const double* __restrict__ partial, int nblk, long n,
                                                                long n0, float* __restrict__ out0,
                                                                float* __restrict__ out1, int accumulate) {
-  __shared__ double red[16][16];
-  const int g = threadIdx.x >> 4, k = threadIdx.x & 15;
-  const long i = (long)blockIdx.x * 16 + k;
-  double s = 0.0;
-  if (i < n)
-    s = strided_sum(partial + i, g, nblk, 16, (size_t)n, s);
-  red[g][k] = s;
-  __syncthreads();
-  if (g == 0 && i < n) {
-    double t = red[0][k];
-#pragma unroll
-    for (int q = 1; q < 16; ++q) t += red[q][k];
+  const long i = (long)blockIdx.x * 16 + (threadIdx.x & 15);
+  double t;
+  if (chain_sum<16>(partial + i, i < n, nblk, (size_t)n, t)) {
     float* o = i < n0 ? out0 + i : out1 + (i - n0);
     *o = accumulate ? *o + (float)t : (float)t;
   }
@@ -270,11 +261,10 @@ __global__ __launch_bounds__(kTB) void layer_norm_fwd_kernel(const float* __rest
 __global__ __launch_bounds__(kTB) void layer_norm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                              long T, const float* __restrict__ g, long tpb,
                                                              float* __restrict__ dx, double* __restrict__ partial) {
-  __shared__ double red[64][kTB / 64];
   const long t0 = (long)blockIdx.x * tpb, t1 = t0 + tpb < T ? t0 + tpb : T;
-  float pg[32], pb[32];
+  float pgb[64];  // sums of dy*xhat [0, 32) and of dy [32, 64)
 #pragma unroll
-  for (int i = 0; i < 32; ++i) pg[i] = pb[i] = 0.f;
+  for (int i = 0; i < 64; ++i) pgb[i] = 0.f;
   for (long t = t0 + threadIdx.x; t < t1; t += kTB) {
     float v[32], d[32];
 #pragma unroll
@@ -299,8 +289,8 @@ __global__ __launch_bounds__(kTB) void layer_norm_bwd_kernel(const float* __rest
       const float gy = d[i] * g[i];
       s1 += gy;
       s2 = fmaf(gy, xh, s2);
-      pg[i] = fmaf(d[i], xh, pg[i]);
-      pb[i] += d[i];
+      pgb[i] = fmaf(d[i], xh, pgb[i]);
+      pgb[32 + i] += d[i];
     }
     float o[32];
 #pragma unroll
@@ -312,17 +302,7 @@ __global__ __launch_bounds__(kTB) void layer_norm_bwd_kernel(const float* __rest
     for (int i = 0; i < 32; i += 4)
       *reinterpret_cast<float4*>(dx + t * 32 + i) = make_float4(o[i], o[i + 1], o[i + 2], o[i + 3]);
   }
-  // fp64 block reduction of the 64 per-thread sums (fixed butterfly per wave, then the 4 waves in order)
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 64; ++i) {
-    const double val = wave_xor_sum_dpp((double)(i < 32 ? pg[i] : pb[i - 32]));  // the fixed xor butterfly (common.h)
-    if (lane == 0) red[i][wv] = val;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64)
-    partial[(size_t)blockIdx.x * 64 + threadIdx.x] =
-        (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+  block_sum_store<true>(pgb, partial + (size_t)blockIdx.x * 64);
 }
 
 // Thread layout of the three token kernels below: thread = (token slot, head) with head = threadIdx & 7, so
@@ -473,16 +453,13 @@ __global__ __launch_bounds__(kTB) void linattn_bwd_kv_kernel(const float* __rest
   *reinterpret_cast<float4*>(dv + s * 32 + h * 4) = make_float4(ov[0], ov[1], ov[2], ov[3]);
 }
 
-static long tok_chunk(long T, long maxblk, long c = 1024) {
-  while ((T + c - 1) / c > maxblk) c *= 2;
-  return c;
-}
+// token ranges of the partial passes (chunk_for, train_reduce.h)
+static Chunk token_wgrad_chunk(long T) { return chunk_for(T, 256, 512); }
+static Chunk layer_norm_chunk(long T) { return chunk_for(T, 256, 1024); }
 
 }  // namespace tmvs
 
 using namespace tmvs;
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 static int token_linear_impl(const float* x, long tokens, int in_features, int out_features, const float* w,
                              const float* b, int transpose_w, const float* relu_of, int accumulate, const float* res,
@@ -521,16 +498,14 @@ extern "C" int tmvs_token_linear_res(const float* x, long tokens, int in_feature
 }
 
 extern "C" size_t tmvs_token_wgrad_workspace(long tokens, int a, int b) {
-  const long c = tok_chunk(tokens, 512, 256);
-  return (size_t)((tokens + c - 1) / c) * (a * b + a) * sizeof(double);
+  return (size_t)token_wgrad_chunk(tokens).blocks * (a * b + a) * sizeof(double);
 }
 
 extern "C" int tmvs_token_wgrad(const float* dy, int a, const float* x, int b, long tokens, void* workspace,
                                 size_t workspace_bytes, float* dw, float* db, int accumulate, void* stream) {
   if (!dy || !x || !workspace || !dw || !db || tokens <= 0) return TMVS_ERR_ARG;
   if (workspace_bytes < tmvs_token_wgrad_workspace(tokens, a, b)) return TMVS_ERR_ARG;
-  const long c = tok_chunk(tokens, 512, 256);
-  const int nblk = (int)((tokens + c - 1) / c);
+  const auto [c, nblk] = token_wgrad_chunk(tokens);
   hipStream_t st = (hipStream_t)stream;
   double* part = (double*)workspace;
 #define TMVS_TW(A, B, TA, TB)                                                                                   \
@@ -560,8 +535,7 @@ extern "C" int tmvs_layer_norm_fwd(const float* x, long tokens, const float* g, 
 }
 
 extern "C" size_t tmvs_layer_norm_bwd_workspace(long tokens) {
-  const long c = tok_chunk(tokens, 1024, 256);
-  return (size_t)((tokens + c - 1) / c) * 64 * sizeof(double);
+  return (size_t)layer_norm_chunk(tokens).blocks * 64 * sizeof(double);
 }
 
 extern "C" int tmvs_layer_norm_bwd(const float* dy, const float* x, long tokens, const float* g, void* workspace,
@@ -569,8 +543,7 @@ extern "C" int tmvs_layer_norm_bwd(const float* dy, const float* x, long tokens,
   if (!dy || !x || !g || !workspace || !dx || !dgb || tokens <= 0) return TMVS_ERR_ARG;
   if (!aligned16(dy) || !aligned16(x) || !aligned16(dx)) return TMVS_ERR_ARG;
   if (workspace_bytes < tmvs_layer_norm_bwd_workspace(tokens)) return TMVS_ERR_ARG;
-  const long c = tok_chunk(tokens, 1024, 256);
-  const int nblk = (int)((tokens + c - 1) / c);
+  const auto [c, nblk] = layer_norm_chunk(tokens);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(layer_norm_bwd_kernel, dim3(nblk), dim3(kTB), 0, st, dy, x, tokens, g, c, dx, (double*)workspace);
   TMVS_CHECK_LAUNCH();

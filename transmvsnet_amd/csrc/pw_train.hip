@@ -9,7 +9,7 @@
 // Per-view statistics ("st", fp32): mean0[16] var0[16] mean1[8] var1[8] (biased variances).
 // Every reduction is fp64 block partials + a fixed-order combine (deterministic, no atomics);
 // the backward recomputes the forward chain per element instead of storing 24 channels per voxel.
-#include "common.h"
+#include "train_reduce.h"
 
 namespace tmvs {
 
@@ -67,44 +67,6 @@ __device__ __forceinline__ void pw_chain(float s, const float* __restrict__ p, c
   c.sg = 1.f / (1.f + expf(-c.o));
 }
 
-// fp64 block reduction of NV values per thread into partial[blockIdx.x][NV]: a fixed xor butterfly
-// inside each wave, then the 4 wave sums in a fixed order (deterministic). The DPP moves for the 160-value
-// pass-2 and the 16-value pass-3 / z1 reductions: with 25 values (pass 1) they raised it to 178 VGPRs
-template <typename T, int NV>
-__device__ __forceinline__ void block_reduce_store(const T (&v)[NV], double* __restrict__ partial) {
-  constexpr bool kDpp = NV >= 64 || NV == 16;  // common.h's DPP butterfly (r15a)
-  __shared__ double red[kPwBlock / 64][NV];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    double x = (double)v[i];
-    if constexpr (kDpp) {
-      x = wave_xor_sum_dpp(x);
-    } else {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    }
-    if (lane == 0) red[wv][i] = x;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < NV; i += kPwBlock)
-    partial[(size_t)blockIdx.x * NV + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-}
-
-__global__ __launch_bounds__(kPwBlock) void pw_sum_partials_kernel(const double* __restrict__ partial, int nblk, int K,
-                                                                   double* __restrict__ out) {
-  __shared__ double red[kPwBlock];
-  double a = 0.0;
-  a = strided_sum(partial + blockIdx.x, threadIdx.x, nblk, kPwBlock, (size_t)K, a);
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int st = kPwBlock / 2; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = red[0];
-}
-
 // ---------------------------------------------------------------- forward
 // stats of s (sum, sum^2) -> layer-0 statistics mean0 = w0*mean_s, var0 = w0^2 * var_s
 __global__ __launch_bounds__(kPwBlock) void pw_s_partial_kernel(const float* __restrict__ s, long n, long vpb,
@@ -116,7 +78,7 @@ __global__ __launch_bounds__(kPwBlock) void pw_s_partial_kernel(const float* __r
     v[0] += x;
     v[1] += x * x;
   }
-  block_reduce_store(v, partial);
+  block_sum_store<false>(v, partial + (size_t)blockIdx.x * 2);
 }
 
 __global__ void pw_stats0_kernel(const double* __restrict__ sums, long n, const float* __restrict__ p,
@@ -148,7 +110,7 @@ __global__ __launch_bounds__(kPwBlock) void pw_z1_partial_kernel(const float* __
       v[8 + k] += (double)z1[k] * (double)z1[k];
     }
   }
-  block_reduce_store(v, partial);
+  block_sum_store<true>(v, partial + (size_t)blockIdx.x * 16);
 }
 
 __global__ void pw_stats1_kernel(const double* __restrict__ sums, long n, float* __restrict__ st) {
@@ -252,7 +214,8 @@ __global__ __launch_bounds__(kPwBlock) void pw_bwd1_kernel(const float* __restri
     }
     v[24] += (double)go;
   }
-  block_reduce_store(v, partial);
+  // the __shfl_xor butterfly: with 25 values the DPP moves raised this kernel to 178 VGPRs (train_reduce.h)
+  block_sum_store<false>(v, partial + (size_t)blockIdx.x * 25);
 }
 
 // the layer-1 gradient of one element: dz1 = a1 (g1 - S1a/N - xhat1 S1b/N), g1 nonzero at the argmax only
@@ -306,7 +269,7 @@ __global__ __launch_bounds__(kPwBlock) void pw_bwd2_kernel(const float* __restri
       acc[16 + j] = fmaf(g0, xhat0, acc[16 + j]);
     }
   }
-  block_reduce_store(acc, partial);
+  block_sum_store<true>(acc, partial + (size_t)blockIdx.x * 160);
 }
 
 // pass 3 (per element): dz0 = a0 (g0 - S0a/N - xhat0 S0b/N); dsims += sum_j w0_j dz0_j; sums of dz0*s (16)
@@ -345,7 +308,7 @@ __global__ __launch_bounds__(kPwBlock) void pw_bwd3_kernel(const float* __restri
     }
     dsims[e] = dsims[e] + ds;
   }
-  block_reduce_store(v, partial);
+  block_sum_store<true>(v, partial + (size_t)blockIdx.x * 16);
 }
 
 // parameter gradients of this view, added to grad[201] (pwp layout)
@@ -366,11 +329,8 @@ __global__ void pw_grad_finalize_kernel(const double* __restrict__ s1, const dou
   if (t == 0) grad[PW_B2] += (float)s1[24];
 }
 
-static long pw_chunk(long n, long maxblk) {
-  long c = 1024;
-  while ((n + c - 1) / c > maxblk) c *= 2;
-  return c;
-}
+// element / pixel ranges of the partial passes: at most the 1024 blocks the workspace holds
+static Chunk pw_chunk(long n) { return chunk_for(n, 1024, 1024); }
 
 }  // namespace tmvs
 
@@ -391,16 +351,15 @@ extern "C" int tmvs_pixelwise_train_forward(const float* sims, int n_views, int 
   const long n = (long)ndepth * P;
   double* part = (double*)workspace;
   double* sums = part + 1024 * 160;
-  const long c = pw_chunk(n, 1024);
-  const int nb = (int)((n + c - 1) / c);
+  const auto [c, nb] = pw_chunk(n);
   for (int v = 0; v < n_views; ++v) {
     const float* s = sims + (size_t)v * n;
     float* sv = stats + (size_t)v * 48;
     hipLaunchKernelGGL(pw_s_partial_kernel, dim3(nb), dim3(kPwBlock), 0, st, s, n, c, part);
-    hipLaunchKernelGGL(pw_sum_partials_kernel, dim3(2), dim3(kPwBlock), 0, st, (const double*)part, nb, 2, sums);
+    hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(2), dim3(kPwBlock), 0, st, (const double*)part, nb, 2, sums);
     hipLaunchKernelGGL(pw_stats0_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, n, pwp, sv);
     hipLaunchKernelGGL(pw_z1_partial_kernel, dim3(nb), dim3(kPwBlock), 0, st, s, n, c, pwp, (const float*)sv, part);
-    hipLaunchKernelGGL(pw_sum_partials_kernel, dim3(16), dim3(kPwBlock), 0, st, (const double*)part, nb, 16, sums);
+    hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(16), dim3(kPwBlock), 0, st, (const double*)part, nb, 16, sums);
     hipLaunchKernelGGL(pw_stats1_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, n, sv);
     hipLaunchKernelGGL(pw_weight_kernel, dim3((P + kPwBlock - 1) / kPwBlock), dim3(kPwBlock), 0, st, s, ndepth, P,
                        pwp, (const float*)sv, view_w + (size_t)v * P, dstar + (size_t)v * P);
@@ -449,8 +408,8 @@ extern "C" int tmvs_pixelwise_train_backward(const float* sims, int n_views, int
   double* s1 = part + 1024 * 160;
   double* s2 = s1 + 32;
   double* s3 = s2 + 160;
-  const long cp = pw_chunk(P, 1024), ce = pw_chunk(n, 1024);
-  const int nbp = (int)((P + cp - 1) / cp), nbe = (int)((n + ce - 1) / ce);
+  const auto [cp, nbp] = pw_chunk(P);
+  const auto [ce, nbe] = pw_chunk(n);
   for (int v = 0; v < n_views; ++v) {
     const float* s = sims + (size_t)v * n;
     const float* sv = stats + (size_t)v * 48;
@@ -458,13 +417,13 @@ extern "C" int tmvs_pixelwise_train_backward(const float* sims, int n_views, int
     const int* ds = dstar + (size_t)v * P;
     const float* dw = dview_w + (size_t)v * P;
     hipLaunchKernelGGL(pw_bwd1_kernel, dim3(nbp), dim3(kPwBlock), 0, st, s, ndepth, P, pwp, sv, w, ds, dw, cp, part);
-    hipLaunchKernelGGL(pw_sum_partials_kernel, dim3(25), dim3(kPwBlock), 0, st, (const double*)part, nbp, 25, s1);
+    hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(25), dim3(kPwBlock), 0, st, (const double*)part, nbp, 25, s1);
     hipLaunchKernelGGL(pw_bwd2_kernel, dim3(nbe), dim3(kPwBlock), 0, st, s, ndepth, P, pwp, sv, w, ds, dw,
                        (const double*)s1, ce, part);
-    hipLaunchKernelGGL(pw_sum_partials_kernel, dim3(160), dim3(kPwBlock), 0, st, (const double*)part, nbe, 160, s2);
+    hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(160), dim3(kPwBlock), 0, st, (const double*)part, nbe, 160, s2);
     hipLaunchKernelGGL(pw_bwd3_kernel, dim3(nbe), dim3(kPwBlock), 0, st, s, ndepth, P, pwp, sv, w, ds, dw,
                        (const double*)s1, (const double*)s2, ce, dsims + (size_t)v * n, part);
-    hipLaunchKernelGGL(pw_sum_partials_kernel, dim3(16), dim3(kPwBlock), 0, st, (const double*)part, nbe, 16, s3);
+    hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(16), dim3(kPwBlock), 0, st, (const double*)part, nbe, 16, s3);
     hipLaunchKernelGGL(pw_grad_finalize_kernel, dim3(1), dim3(128), 0, st, (const double*)s1, (const double*)s2,
                        (const double*)s3, dpwp);
     TMVS_CHECK_LAUNCH();
