@@ -638,6 +638,64 @@ int tmvs_nearest_up2_backward_nhwc(const float* d, int n, int h, int w, int chan
 int tmvs_softmax_backward(const float* prob, const float* dprob, int batch, int ndepth, int height, int width,
                           float* dlogits, void* stream);
 
+/* ------------------------------------------------------------------ DTU evaluation (DTU-MATLAB/)
+ * Accuracy / completeness of a fused cloud against the DTU ground truth: the spatial searches of
+ * reducePts_haa.m and MaxDistCP.m and the two point predicates of PointCompareMain.m.
+ * transmvsnet_amd.dtu_eval drives them; DESIGN.md "DTU evaluation" has the algorithm. Point clouds are
+ * [n][3] float32; every comparison is fp64 on squared distances, dx = (double)a.x - (double)b.x,
+ * d2 = (dx*dx + dy*dy) + dz*dz, unfused. n < 2^31 - 256 (TMVS_ERR_SHAPE beyond). These entry points are
+ * additions: no earlier signature or behaviour changes with them, so TMVS_ABI_VERSION stays as it was.
+ *
+ * A grid is HOST double[4] = {origin x, y, z, cell edge}. A point's cell is floor((p - origin) / cell) per
+ * axis in fp64, clamped to [-2^20, 2^20); its key is ((ix + 2^20) << 42) | ((iy + 2^20) << 21) | (iz + 2^20).
+ *
+ * tmvs_dtu_cell_keys: keys [n] int64 of xyz under grid. The caller sorts them.
+ * tmvs_dtu_gather_points: points4 [n][4] (16-byte aligned) = {xyz[order[i]], payload as int32 bits}:
+ *   payload[order[i]] when payload is given, else order[i]. order [n] int64 is the sorting permutation.
+ * tmvs_dtu_grid_table: from the ascending keys and head_rank [n] int64 = the inclusive prefix count of
+ *   run heads (key[i] != key[i-1], and i = 0), whose last element is n_cells, writes the table: n_cells
+ *   int64 unique keys, then n_cells + 1 int32 run starts (the last one = n). table is 8-byte aligned device
+ *   memory of at least tmvs_dtu_grid_table_bytes(n_cells) bytes (0 for n_cells <= 0), else TMVS_ERR_ARG.
+ * tmvs_dtu_thin_round: one round of reducePts_haa.m:17-31 over points4 sorted by key with payload = the
+ *   point's rank in the visiting order (distinct). state_in / state_out [n] uint8 in sorted order, distinct
+ *   buffers: an UNDECIDED point becomes REMOVED when a point of smaller rank within radius (d2 <=
+ *   radius^2) is KEPT, KEPT when every such point is REMOVED, and stays UNDECIDED otherwise; decided points
+ *   are copied. *undecided (device int32, zeroed by the caller) is increased by the number of points left
+ *   UNDECIDED. radius must be smaller than the cell edge (TMVS_ERR_ARG): the 3x3x3 cells round a point then
+ *   hold every point within radius. Start from all UNDECIDED and repeat until the count is 0; every round
+ *   decides at least the undecided point of smallest rank.
+ * tmvs_dtu_nearest_pass: refines d2 [n_from] float64 (indexed by the from-point's payload = its original
+ *   index) in place with min(d2, squared distance to the nearest to-point), searching rings 0..max_ring of
+ *   grid cells round the from-point and stopping at the first ring whose inner distance reaches d2. Only
+ *   from-points with d2 > skip_below and inside [BB1, BB1 + (floor((BB2 - BB1) / block) + 1) * block)
+ *   (bb HOST double[6] = BB1, BB2; MaxDistCP.m:5-17) are searched. With d2 initialised to max_dist^2 and a
+ *   last pass whose max_ring covers max_dist, d2 is exact where the nearest to-point is nearer than max_dist
+ *   and max_dist^2 elsewhere. from4 is in any order (cell order makes a wave's lanes walk the same cells);
+ *   to4 and table are the to-points sorted under grid. max_dist > block is TMVS_ERR_ARG; more than
+ *   TMVS_DTU_MAX_RING rings (after max_ring is capped at ceil(max_dist / cell) + 2) is TMVS_ERR_SHAPE.
+ * tmvs_dtu_in_mask: out[i] = 1 when Qv = round((xyz - bb_low) / res + 1) (half away from zero) lies in
+ *   1..size on every axis and mask[Qv - 1] != 0, mask [size_x][size_y][size_z] uint8 (PointCompareMain.m:37-45).
+ * tmvs_dtu_above_plane: out[i] = ((P0 x + P1 y) + P2 z) + P3 > 0, plane HOST double[4] (:57).          */
+#define TMVS_DTU_UNDECIDED 0
+#define TMVS_DTU_KEPT 1
+#define TMVS_DTU_REMOVED 2
+#define TMVS_DTU_MAX_RING 64
+int tmvs_dtu_cell_keys(const float* xyz, long n, const double* grid, long long* keys, void* stream);
+int tmvs_dtu_gather_points(const float* xyz, const long long* order, const int* payload, long n, float* points4,
+                           void* stream);
+size_t tmvs_dtu_grid_table_bytes(long n_cells);
+int tmvs_dtu_grid_table(const long long* sorted_keys, const long long* head_rank, long n, long n_cells, void* table,
+                        size_t table_bytes, void* stream);
+int tmvs_dtu_thin_round(const float* points4, long n, const void* table, long n_cells, const double* grid,
+                        double radius, const unsigned char* state_in, unsigned char* state_out, int* undecided,
+                        void* stream);
+int tmvs_dtu_nearest_pass(const float* from4, long n_from, const float* to4, long n_to, const void* table,
+                          long n_cells, const double* grid, const double* bb, double max_dist, double block,
+                          int max_ring, double skip_below, double* d2, void* stream);
+int tmvs_dtu_in_mask(const float* xyz, long n, const unsigned char* mask, int size_x, int size_y, int size_z,
+                     const double* bb_low, double res, unsigned char* out, void* stream);
+int tmvs_dtu_above_plane(const float* xyz, long n, const double* plane, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,14 @@ SIGNATURES = {
     "tmvs_dcn_backward_set": (I, [P, P, P, P, I, I, I, I, I, P, S, P, P, P, P, P]),
     "tmvs_nearest_up2_backward_nhwc": (I, [P, I, I, I, I, I, P, P]),
     "tmvs_softmax_backward": (I, [P, P, I, I, I, I, P, P]),
+    "tmvs_dtu_cell_keys": (I, [P, L, P, P, P]),
+    "tmvs_dtu_gather_points": (I, [P, P, P, L, P, P]),
+    "tmvs_dtu_grid_table_bytes": (S, [L]),
+    "tmvs_dtu_grid_table": (I, [P, P, L, L, P, S, P]),
+    "tmvs_dtu_thin_round": (I, [P, L, P, L, P, D, P, P, P, P]),
+    "tmvs_dtu_nearest_pass": (I, [P, L, P, L, P, L, P, P, D, D, I, D, P, P]),
+    "tmvs_dtu_in_mask": (I, [P, L, P, I, I, I, P, D, P, P]),
+    "tmvs_dtu_above_plane": (I, [P, L, P, P, P]),
 }
 
 ABI_VERSION = 11
@@ -124,6 +132,7 @@ DYNFUSE_PAIR_FLOATS = 64
 DYNFUSE_REF_FLOATS = 24
 DYNFUSE_MAX_SRC = 10
 DYNFUSE_PHOTO, DYNFUSE_GEO, DYNFUSE_FINAL = 1, 2, 4
+DTU_UNDECIDED, DTU_KEPT, DTU_REMOVED = 0, 1, 2
 
 
 class CostRegWeights(ctypes.Structure):

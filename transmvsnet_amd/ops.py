@@ -1288,3 +1288,134 @@ for _name in ("conv2d_generic", "conv2d_wgrad", "colsum", "dcn_forward_train", "
               "nearest_up2_backward_nhwc", "softmax_backward"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name
+
+
+# ----------------------------------------------------------------- DTU evaluation (csrc/dtu_eval.hip)
+def _dtu_t(t, name, dtype, shape=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a GPU tensor (the HIP path has no CPU fallback)")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous {dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, not {tuple(t.shape)}")
+    return t
+
+
+def _dtu_xyz(t, name):
+    _dtu_t(t, name, torch.float32)
+    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] == 0:
+        raise ValueError(f"{name} must be [N, 3] with N >= 1")
+    return t.shape[0]
+
+
+def _dtu_host(values, n, name):
+    a = np.ascontiguousarray(np.asarray(values, np.float64).reshape(-1))
+    if a.size != n:
+        raise ValueError(f"{name} must hold {n} numbers")
+    return a
+
+
+def dtu_cell_keys(xyz, grid):
+    """tmvs_dtu_cell_keys: xyz [N,3] -> int64 [N] cell keys under grid = (origin x, y, z, cell edge)."""
+    n = _dtu_xyz(xyz, "xyz")
+    g = _dtu_host(grid, 4, "grid")
+    keys = torch.empty(n, dtype=torch.int64, device=xyz.device)
+    with _Span("tmvs_dtu_cell_keys"):
+        _lib.check(_lib_h().tmvs_dtu_cell_keys(_ptr(xyz), n, g.ctypes.data, _ptr(keys), _stream()), "tmvs_dtu_cell_keys")
+    return keys
+
+
+def dtu_gather_points(xyz, order, payload=None):
+    """tmvs_dtu_gather_points: float32 [N,4] records (xyz[order], int32 payload bits) in sorted order."""
+    n = _dtu_xyz(xyz, "xyz")
+    _dtu_t(order, "order", torch.int64, (n,))
+    if payload is not None:
+        _dtu_t(payload, "payload", torch.int32, (n,))
+    pts = torch.empty(n, 4, dtype=torch.float32, device=xyz.device)
+    with _Span("tmvs_dtu_gather_points"):
+        _lib.check(_lib_h().tmvs_dtu_gather_points(_ptr(xyz), _ptr(order), _ptr(payload), n, _ptr(pts), _stream()),
+                   "tmvs_dtu_gather_points")
+    return pts
+
+
+def dtu_grid_table(sorted_keys, head_rank, n_cells):
+    """tmvs_dtu_grid_table: the unique keys and run starts of ascending keys, as one int64 buffer."""
+    _dtu_t(sorted_keys, "sorted_keys", torch.int64)
+    n = sorted_keys.numel()
+    _dtu_t(head_rank, "head_rank", torch.int64, (n,))
+    nbytes = _lib_h().tmvs_dtu_grid_table_bytes(int(n_cells))
+    if nbytes == 0:
+        raise ValueError("dtu_grid_table: n_cells must be positive")
+    table = torch.empty(nbytes // 8, dtype=torch.int64, device=sorted_keys.device)
+    with _Span("tmvs_dtu_grid_table"):
+        _lib.check(_lib_h().tmvs_dtu_grid_table(_ptr(sorted_keys), _ptr(head_rank), n, int(n_cells), _ptr(table), nbytes,
+                                                _stream()), "tmvs_dtu_grid_table")
+    return table
+
+
+def dtu_thin_round(points4, table, n_cells, grid, radius, state_in, state_out, undecided):
+    """tmvs_dtu_thin_round: one round of the thinning; adds the points left undecided to `undecided`."""
+    _dtu_t(points4, "points4", torch.float32)
+    n = points4.shape[0]
+    _dtu_t(table, "table", torch.int64)
+    _dtu_t(state_in, "state_in", torch.uint8, (n,))
+    _dtu_t(state_out, "state_out", torch.uint8, (n,))
+    _dtu_t(undecided, "undecided", torch.int32, (1,))
+    g = _dtu_host(grid, 4, "grid")
+    if points4.dim() != 2 or points4.shape[1] != 4 or table.numel() * 8 < _lib_h().tmvs_dtu_grid_table_bytes(int(n_cells)):
+        raise ValueError("dtu_thin_round: points4 must be [N, 4] and table must hold n_cells cells")
+    with _Span("tmvs_dtu_thin_round"):
+        _lib.check(_lib_h().tmvs_dtu_thin_round(_ptr(points4), n, _ptr(table), int(n_cells), g.ctypes.data,
+                                                float(radius), _ptr(state_in), _ptr(state_out), _ptr(undecided),
+                                                _stream()), "tmvs_dtu_thin_round")
+
+
+def dtu_nearest_pass(from4, to4, table, n_cells, grid, bb, max_dist, block, max_ring, skip_below, d2):
+    """tmvs_dtu_nearest_pass: refine d2 [N_from] float64 in place against the to-points' grid."""
+    _dtu_t(from4, "from4", torch.float32)
+    _dtu_t(to4, "to4", torch.float32)
+    _dtu_t(table, "table", torch.int64)
+    if from4.dim() != 2 or from4.shape[1] != 4 or to4.dim() != 2 or to4.shape[1] != 4:
+        raise ValueError("dtu_nearest_pass: from4 and to4 must be [N, 4]")
+    _dtu_t(d2, "d2", torch.float64, (from4.shape[0],))
+    if table.numel() * 8 < _lib_h().tmvs_dtu_grid_table_bytes(int(n_cells)):
+        raise ValueError("dtu_nearest_pass: table must hold n_cells cells")
+    g = _dtu_host(grid, 4, "grid")
+    b = _dtu_host(bb, 6, "bb")
+    with _Span("tmvs_dtu_nearest_pass"):
+        _lib.check(_lib_h().tmvs_dtu_nearest_pass(_ptr(from4), from4.shape[0], _ptr(to4), to4.shape[0], _ptr(table),
+                                                  int(n_cells), g.ctypes.data, b.ctypes.data, float(max_dist),
+                                                  float(block), int(max_ring), float(skip_below), _ptr(d2), _stream()),
+                   "tmvs_dtu_nearest_pass")
+    return d2
+
+
+def dtu_in_mask(xyz, mask, bb_low, res):
+    """tmvs_dtu_in_mask: xyz [N,3], mask uint8 [X,Y,Z] -> uint8 [N] (PointCompareMain.m:37-45)."""
+    n = _dtu_xyz(xyz, "xyz")
+    _dtu_t(mask, "mask", torch.uint8)
+    if mask.dim() != 3 or mask.numel() == 0:
+        raise ValueError("mask must be [X, Y, Z]")
+    b = _dtu_host(bb_low, 3, "bb_low")
+    out = torch.empty(n, dtype=torch.uint8, device=xyz.device)
+    with _Span("tmvs_dtu_in_mask"):
+        _lib.check(_lib_h().tmvs_dtu_in_mask(_ptr(xyz), n, _ptr(mask), *mask.shape, b.ctypes.data, float(res), _ptr(out),
+                                             _stream()), "tmvs_dtu_in_mask")
+    return out
+
+
+def dtu_above_plane(xyz, plane):
+    """tmvs_dtu_above_plane: xyz [N,3], plane (4 numbers) -> uint8 [N] (PointCompareMain.m:57)."""
+    n = _dtu_xyz(xyz, "xyz")
+    p = _dtu_host(plane, 4, "plane")
+    out = torch.empty(n, dtype=torch.uint8, device=xyz.device)
+    with _Span("tmvs_dtu_above_plane"):
+        _lib.check(_lib_h().tmvs_dtu_above_plane(_ptr(xyz), n, p.ctypes.data, _ptr(out), _stream()),
+                   "tmvs_dtu_above_plane")
+    return out
+
+
+for _name in ("dtu_cell_keys", "dtu_gather_points", "dtu_grid_table", "dtu_thin_round", "dtu_nearest_pass", "dtu_in_mask",
+              "dtu_above_plane"):
+    globals()[_name] = _on_tensor_device(globals()[_name])
+del _name
