@@ -196,6 +196,13 @@ int tmvs_fmt_kv_grouped(const float* source, int nv, int group_nv, int s_tokens,
  * (cross layers: the ref view's K/V serve every source view). */
 int tmvs_fmt_apply(float* x, int nv, int l_tokens, const float* kv, long kv_view_stride, const float* enc_w,
                    void* stream);
+/* tmvs_fmt_apply with an explicit tiling: tiles_per_wave > 0 is the number of 16-token tiles each wave of a
+ * 4-wave workgroup walks; 0 sizes it from the kernel's occupancy, as tmvs_fmt_apply does. The arithmetic is
+ * per token, so x is bitwise the same for every tiling. (tmvs_fmt_forward_split uses it; the tests reach the
+ * kernel's multi-tile paths with it at small shapes.) An addition: no earlier signature or behaviour changes
+ * with it, so TMVS_ABI_VERSION stays as it was. */
+int tmvs_fmt_apply_tiled(float* x, int nv, int l_tokens, const float* kv, long kv_view_stride, const float* enc_w,
+                         int tiles_per_wave, void* stream);
 
 /* FMT_with_pathway lateral step (models/FMT.py:221-228): out = smooth(up2(reduce(coarse)) + lateral)
  *   coarse [nv][h][w][cc] (NHWC), lateral [nv][cf][2h][2w] (NCHW, per-view stride lat_view_stride),

@@ -93,6 +93,19 @@ def test_argument_validation_without_gpu(lib):
     assert lib.tmvs_fmt_kv_grouped_workspace(1, 1, L) == lib.tmvs_fmt_kv_workspace(1, L)
     assert lib.tmvs_fmt_kv_grouped_workspace(0, 5, L) == 0
     assert lib.tmvs_fmt_kv_grouped(None, 1, 5, L, None, None, 0, None, None) == -1
+    # the apply with an explicit tiling: declared, bound with its 8 arguments, and it validates like tmvs_fmt_apply
+    # (the pointers are host memory that is never read; every call has exactly one thing wrong with it)
+    assert _declarations()["tmvs_fmt_apply_tiled"] == len(_lib.SIGNATURES["tmvs_fmt_apply_tiled"][1]) == 8
+    backing = np.zeros(64, np.float32)
+    p = backing.ctypes.data
+    for tiled in (lib.tmvs_fmt_apply_tiled, lambda *a: lib.tmvs_fmt_apply(*a[:6], a[7])):
+        for tpw in (0, 1, 3):
+            for nul in range(3):  # x, kv, enc_w
+                a = [p, p, p]
+                a[nul] = None
+                assert tiled(a[0], 1, 16, a[1], 160, a[2], tpw, None) == -1, (nul, tpw)
+            for nv, l, stride in ((0, 16, 160), (-1, 16, 160), (1, 0, 160), (1, -1, 160), (1, 16, -1)):
+                assert tiled(p, nv, l, p, stride, p, tpw, None) == -1, (nv, l, stride, tpw)
     # the split FMT needs both K/V slabs; NULL side stream falls back to (and validates like) tmvs_fmt_forward
     assert lib.tmvs_fmt_forward_split_workspace(5, L) > lib.tmvs_fmt_forward_workspace(5, L)
     assert lib.tmvs_fmt_forward_split_workspace(1, L) == lib.tmvs_fmt_forward_workspace(1, L)

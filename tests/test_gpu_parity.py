@@ -354,8 +354,9 @@ def test_fmt_forward_split_bitwise(model, nv, h, w):
         assert torch.equal(kv, kv_all[lo:hi]), f"grouped K/V views {lo}..{hi}"
 
 
-# (views, coarse h, w): one partial tile row; ragged tiles over 798 tiles, i.e. runs of 2 tiles per
-# workgroup of the pipelined stage-2 kernel with a short last run
+# (views, coarse h, w): 12 tiles with a partial last row and column; 3 x 14 x 19 = 798 tiles of pathway16_mfma_kernel, one
+# workgroup each, ragged along both axes (218 x 294 outputs). The tails, the stage-3 kernel and strided
+# laterals are in tests/test_gpu_fmt_layers.py.
 @pytest.mark.parametrize("nv,h,w", [(2, 12, 20), (3, 109, 147)])
 def test_fmt_pathway(sd, model, nv, h, w):
     torch.manual_seed(3)

@@ -36,6 +36,7 @@ SIGNATURES = {
     "tmvs_fmt_kv_workspace": (S, [I, I]),
     "tmvs_fmt_kv": (I, [P, I, I, P, P, S, P, P]),
     "tmvs_fmt_apply": (I, [P, I, I, P, L, P, P]),
+    "tmvs_fmt_apply_tiled": (I, [P, I, I, P, L, P, I, P]),
     "tmvs_fmt_pathway": (I, [P, P, L, P, P, I, I, I, I, I, P, P]),
     "tmvs_fmt_forward_workspace": (S, [I, I]),
     "tmvs_fmt_forward": (I, [P, L, P, I, I, I, I, I, P, P, S, P, P]),

@@ -636,8 +636,8 @@ extern "C" int tmvs_fmt_kv(const float* source, int nv, int s_tokens, const floa
 }
 
 // tiles_per_wave > 0 overrides the occupancy-sized tiling (the per-token arithmetic, hence the output, is the same)
-int tmvs_fmt_apply_tiled(float* x, int nv, int l_tokens, const float* kv, long kv_view_stride, const float* enc_w,
-                         int tiles_per_wave, void* stream) {
+extern "C" int tmvs_fmt_apply_tiled(float* x, int nv, int l_tokens, const float* kv, long kv_view_stride,
+                                    const float* enc_w, int tiles_per_wave, void* stream) {
   if (!x || !kv || !enc_w || nv <= 0 || l_tokens <= 0 || kv_view_stride < 0) return TMVS_ERR_ARG;
   const int tpw = tiles_per_wave > 0 ? (tiles_per_wave + kApplyNT - 1) / kApplyNT * kApplyNT
                                      : apply_tiles_per_wave(nv, l_tokens);

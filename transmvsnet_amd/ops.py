@@ -361,24 +361,31 @@ def fmt_embed(feat_nchw, pe, out_tokens):
     return out_tokens
 
 
-def fmt_kv(source_tokens, enc_w, out=None):
-    """(KV, Ksum) of one encoder layer over source tokens [nv,S,32] -> [nv,160]."""
+def fmt_kv(source_tokens, enc_w, out=None, group_nv=None):
+    """(KV, Ksum) of one encoder layer over source tokens [nv,S,32] -> [nv,160].
+
+    group_nv: the partial sums are grouped as in a launch over group_nv views (tmvs_fmt_kv_grouped), so a
+    view's K/V is bitwise the same in any subset of those views; None = nv."""
     nv, s, _ = source_tokens.shape
-    nbytes = _lib_h().tmvs_fmt_kv_workspace(nv, s)
+    group_nv = nv if group_nv is None else int(group_nv)
+    nbytes = _lib_h().tmvs_fmt_kv_grouped_workspace(nv, group_nv, s)
     ws = torch.empty(max(1, nbytes // 4), device=source_tokens.device)
     kv = out if out is not None else torch.empty(nv, _lib.KV_NFLOATS, device=source_tokens.device)
     with _Span("tmvs_fmt_kv"):
-        _lib.check(_lib_h().tmvs_fmt_kv(_ptr(source_tokens), nv, s, _ptr(enc_w), _ptr(ws), ws.numel() * 4, _ptr(kv),
-                                        _stream()), "tmvs_fmt_kv")
+        _lib.check(_lib_h().tmvs_fmt_kv_grouped(_ptr(source_tokens), nv, group_nv, s, _ptr(enc_w), _ptr(ws),
+                                                ws.numel() * 4, _ptr(kv), _stream()), "tmvs_fmt_kv_grouped")
     return kv
 
 
-def fmt_apply(x_tokens, kv, enc_w, shared_kv=False):
-    """Rest of EncoderLayer.forward in place on x [nv,L,32] (FMT.py:96-111)."""
+def fmt_apply(x_tokens, kv, enc_w, shared_kv=False, tiles_per_wave=0):
+    """Rest of EncoderLayer.forward in place on x [nv,L,32] (FMT.py:96-111).
+
+    tiles_per_wave > 0 fixes the 16-token tiles each wave walks (tmvs_fmt_apply_tiled; the result is bitwise
+    the same for every tiling); 0 sizes it from the kernel's occupancy."""
     nv, l, _ = x_tokens.shape
     with _Span("tmvs_fmt_apply"):
-        _lib.check(_lib_h().tmvs_fmt_apply(_ptr(x_tokens), nv, l, _ptr(kv), 0 if shared_kv else _lib.KV_NFLOATS,
-                                           _ptr(enc_w), _stream()), "tmvs_fmt_apply")
+        _lib.check(_lib_h().tmvs_fmt_apply_tiled(_ptr(x_tokens), nv, l, _ptr(kv), 0 if shared_kv else _lib.KV_NFLOATS,
+                                                 _ptr(enc_w), int(tiles_per_wave), _stream()), "tmvs_fmt_apply")
     return x_tokens
 
 
