@@ -139,6 +139,18 @@ int tmvs_conv3d_bn_relu(const float* x, int batch, int cin, int d, int h, int w,
 int tmvs_deconv3d_bn_relu_add(const float* x, int batch, int cin, int d, int h, int w, const float* wpk,
                               const float* alpha, const float* shift, int cout, const float* skip, float* y,
                               void* stream);
+/* tmvs_deconv3d_bn_relu_add pinned to one kernel. The 32 -> 16 layer (conv9) has two: the one-tile-per-workgroup
+ * kernel and a persistent one (weights staged in LDS once per workgroup) that tmvs_deconv3d_bn_relu_add takes
+ * where there are at least 1.5 tiles per resident workgroup; y is bitwise the same on both. _generic always runs the
+ * former (any layer). _persistent always runs the latter (TMVS_ERR_SHAPE for another layer); max_workgroups > 0
+ * bounds its grid below the device's residency, so that the tests reach the multi-tile walk at small shapes.
+ * Additions: no earlier signature or behaviour changes with them, so TMVS_ABI_VERSION stays as it was. */
+int tmvs_deconv3d_bn_relu_add_generic(const float* x, int batch, int cin, int d, int h, int w, const float* wpk,
+                                      const float* alpha, const float* shift, int cout, const float* skip, float* y,
+                                      void* stream);
+int tmvs_deconv3d_bn_relu_add_persistent(const float* x, int batch, int cin, int d, int h, int w, const float* wpk,
+                                         const float* alpha, const float* shift, int cout, const float* skip,
+                                         float* y, int max_workgroups, void* stream);
 
 /* ------------------------------------------------------------------ regression
  * prob = exp(log_softmax(logits, D)) (TransMVSNet.py:99); winner-take-all

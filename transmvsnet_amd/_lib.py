@@ -31,6 +31,8 @@ SIGNATURES = {
     "tmvs_costregnet_wta": (I, [P, P, I, I, I, I, P, P, S, F, F, P, P, P, P, P]),
     "tmvs_conv3d_bn_relu": (I, [P, I, I, I, I, I, P, P, P, I, I, P, P]),
     "tmvs_deconv3d_bn_relu_add": (I, [P, I, I, I, I, I, P, P, P, I, P, P, P]),
+    "tmvs_deconv3d_bn_relu_add_generic": (I, [P, I, I, I, I, I, P, P, P, I, P, P, P]),
+    "tmvs_deconv3d_bn_relu_add_persistent": (I, [P, I, I, I, I, I, P, P, P, I, P, P, I, P]),
     "tmvs_softmax_wta": (I, [P, P, I, I, I, I, F, F, P, P, P, P, P]),
     "tmvs_fmt_embed": (I, [P, L, P, I, I, I, I, I, I, P, P]),
     "tmvs_fmt_kv_workspace": (S, [I, I]),

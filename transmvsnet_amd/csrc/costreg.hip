@@ -22,6 +22,8 @@
 // conv0 (Cin 1) and prob (Cout 1) are direct VALU convolutions.
 #include "common.h"
 
+#include <utility>
+
 namespace tmvs {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -63,6 +65,11 @@ struct Buf {
   __device__ __forceinline__ float4 ld4(int voff, int soff = 0) const {
     const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
     return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+  }
+  __device__ __forceinline__ void st4(float4 v, int voff) const {  // an out-of-range lane stores nothing
+    typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+    const uintx4 u{__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+    __builtin_amdgcn_raw_buffer_store_b128(u, r, voff, 0, 0);
   }
   __device__ __forceinline__ float2 ld2(int voff, int soff = 0) const {
     const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
@@ -1324,6 +1331,259 @@ static int launch_deconv_c8(const float* x, const float* w, const float* al, con
   return TMVS_OK;
 }
 
+// ---------------------------------------------------------------- deconv 32 -> 16 (conv9), persistent
+// deconv3d_lds_kernel<32, 16, ...> restages its 27.6 KB of weights per channel chunk and workgroup (107 MB
+// of staging at stages 2 / 3 against 16 MB of input) and overlaps nothing with a workgroup's staging but
+// the other resident workgroups. Here a workgroup stages both chunks' weights once (55.3 KB), then walks
+// its XCD-contiguous share of the tiles as conv3d_c16_kernel does, with both 16-channel planes of a tile
+// in LDS (74.9 KB in all: 2 workgroups per CU) and the next tile committed between two barriers.
+// Every output keeps deconv3d_lds_kernel's K order (chunk, then its class's taps, then the 4 k-steps, one
+// MFMA chain per class), so the results are bitwise the same; only the interleaving of the 8 independent
+// chains differs: the 27 taps of a chunk run as two streams (classes 0, 3, 7 / classes 1, 2, 4, 5, 6)
+// whose MFMAs alternate, so no MFMA waits on the one issued right before it. The 8 distinct B fragments
+// of a chunk (input voxel offsets {0,1}^3) are read from LDS once instead of once per tap.
+// The layer moves about as many bytes as HBM delivers in its MFMA time (143 MB; without the MFMAs the
+// kernel runs 28 us, without the global traffic 34 us), so the memory instructions are spread over the
+// tile's 28 MFMA steps instead of issued in bursts around them: one load per step in the first chunk (this
+// tile's 8 skip voxels, then the next tile's staging loads) and each class's stores right behind its last
+// MFMA in the second. Stage 2 / 3 per call: 53.6 / 52.0 us generic, 48 us for the plain persistent form,
+// 38.5 / 37.7 us as scheduled here.
+struct DeconvTap {
+  int cls, tap, off;  // parity class, weight tap, input voxel offset (bit 2: depth, 1: row, 0: column)
+};
+// tap i (0 .. 12 / 13) of one stream, in deconv3d_lds_kernel's (class, td, th, tw) order
+constexpr DeconvTap deconv_stream_tap(int stream, int i) {
+  int k = 0;
+  for (int cls = 0; cls < 8; ++cls) {
+    if ((cls == 0 || cls == 3 || cls == 7) != (stream == 0)) continue;
+    const int pd = cls >> 2, ph = (cls >> 1) & 1, pw = cls & 1;
+    for (int td = 0; td < 1 + pd; ++td)
+      for (int th = 0; th < 1 + ph; ++th)
+        for (int tw = 0; tw < 1 + pw; ++tw) {
+          const int kd = pd ? (td ? 2 : 0) : 1, od_off = (pd && !td) ? 1 : 0;
+          const int kh = ph ? (th ? 2 : 0) : 1, oh_off = (ph && !th) ? 1 : 0;
+          const int kw = pw ? (tw ? 2 : 0) : 1, ow_off = (pw && !tw) ? 1 : 0;
+          if (k++ == i) return DeconvTap{cls, kd * 9 + kh * 3 + kw, od_off * 4 + oh_off * 2 + ow_off};
+        }
+  }
+  return DeconvTap{-1, 0, 0};
+}
+// the class whose last tap is pair i of its stream (at most one per pair), or -1
+constexpr int deconv_class_done(int i) {
+  for (int st = 0; st < 2; ++st) {
+    const DeconvTap t = deconv_stream_tap(st, i);
+    if (t.cls >= 0 && deconv_stream_tap(st, i + 1).cls != t.cls) return t.cls;
+  }
+  return -1;
+}
+static_assert(deconv_stream_tap(0, 12).cls == 7 && deconv_stream_tap(0, 13).cls < 0, "stream 0: 13 taps");
+static_assert(deconv_stream_tap(1, 13).cls == 6 && deconv_stream_tap(1, 14).cls < 0, "stream 1: 14 taps");
+
+template <typename F, int... I>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+
+template <int TDI, int THI>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void deconv3d_c16p_kernel(
+    const float* __restrict__ x, const float* __restrict__ wpk, const float* __restrict__ alpha,
+    const float* __restrict__ shift, const float* __restrict__ skip, float* __restrict__ y, Geo g, int ntiles) {
+  constexpr int CIN = 32, COUT = 16, PL = 4, NCH = 2;
+  static_assert(TDI * THI == 4, "one input-grid row per wave");
+  constexpr int LW = 17, LH = THI + 1, LD = TDI + 1, VST = 16;
+  constexpr int NVOX = LD * LH * LW;
+  constexpr int NQ = NVOX * 2 * PL;          // float4 quads per tile: a voxel's 32 channels are 8
+  constexpr int NLD = (NQ + 255) / 256;      // staging loads per thread and tile
+  __shared__ __attribute__((aligned(16))) float tile[NCH][NVOX * VST];
+  __shared__ __attribute__((aligned(16))) float wts[NCH][27 * 16 * 16];
+
+  const int nws = (g.Wi + 15) / 16, nhs = (g.Hi + THI - 1) / THI, nds = (g.Di + TDI - 1) / TDI;
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col = lane & 15, kgrp = lane >> 4;
+  // XCD-contiguous tile ranges: workgroup b runs on XCD b % 8 (round-robin dispatch)
+  const int nxcd = gridDim.x >= 8 ? 8 : 1, per_xcd = gridDim.x / nxcd;
+  const int xcd = blockIdx.x % nxcd, kx = blockIdx.x / nxcd;
+  const int t_lo = (int)((long)ntiles * xcd / nxcd), t_hi = (int)((long)ntiles * (xcd + 1) / nxcd);
+  if (kx >= per_xcd) return;  // grid not a multiple of 8: the remainder idles
+
+  struct TileCoord {
+    int n, md0, mh0, mw0;
+  };
+  auto coord = [&](int t) {
+    TileCoord c;
+    c.mw0 = (t % nws) * 16;
+    t /= nws;
+    c.mh0 = (t % nhs) * THI;
+    t /= nhs;
+    c.md0 = (t % nds) * TDI;
+    c.n = t / nds;
+    return c;
+  };
+  const uint32_t in_bytes = (uint32_t)g.Di * g.Hi * g.Wi * CIN * 4;     // one sample (host: < 2 GB)
+  const uint32_t out_bytes = (uint32_t)g.Do * g.Ho * g.Wo * COUT * 4;   // (host: < 2 GB)
+  float4 pf[NLD];
+  // global -> registers, branch-free: lanes outside the volume (and every lane when there is no next
+  // tile) read zeros through the buffer's range check, so the vmcnt waits stay exact
+  struct Fetch {  // the wave-uniform part of a tile's staging loads
+    Buf xb;
+    TileCoord c;
+    int soff;
+    bool live;
+  };
+  auto fetch_of = [&](int t, bool live) {
+    const TileCoord c = coord(live ? t : 0);
+    return Fetch{Buf(x + (size_t)c.n * g.Di * g.Hi * g.Wi * CIN, in_bytes), c,
+                 ((c.md0 * g.Hi + c.mh0) * g.Wi + c.mw0) * CIN * 4 /* the tile's first voxel */, live};
+  };
+  auto fetch1 = [&](const Fetch& f, int k) {
+    const int idx = threadIdx.x + 256 * k;
+    const int vox = idx >> 3, q8 = idx & 7;
+    const int lw = vox % LW, rest = vox / LW, lh = rest % LH, ld = rest / LH;
+    const bool ok = f.live && idx < NQ && f.c.mw0 + lw < g.Wi && f.c.mh0 + lh < g.Hi && f.c.md0 + ld < g.Di;
+    pf[k] = f.xb.ld4(ok ? (((ld * g.Hi + lh) * g.Wi + lw) * CIN + 4 * q8) * 4 : Buf::kOOB, f.soff);
+  };
+  auto fetch = [&](int t, bool live) {
+    const Fetch f = fetch_of(t, live);
+#pragma unroll
+    for (int k = 0; k < NLD; ++k) fetch1(f, k);
+  };
+  auto commit = [&]() {  // registers -> LDS: two 16-channel planes of quad-swizzled voxels
+#pragma unroll
+    for (int k = 0; k < NLD; ++k) {
+      const int idx = threadIdx.x + 256 * k;
+      const int vox = idx >> 3, q8 = idx & 7;
+      const int ch = q8 >> 2, q = q8 & 3;
+      if (idx < NQ) *reinterpret_cast<float4*>(tile[ch] + vox * VST + 4 * (q ^ ((vox >> 1) & 3))) = pf[k];
+    }
+  };
+
+  // the weights: every load in flight at once, with the first tile's behind them (a load -> LDS write loop
+  // paid one L2 round trip per 4 KB, 14 in a row, before the first MFMA)
+  constexpr int NWQ = NCH * 27 * 16 * 4, NWL = (NWQ + 255) / 256;
+  const Buf wb(wpk, 27u * COUT * CIN * 4);
+  float4 wreg[NWL];
+#pragma unroll
+  for (int k = 0; k < NWL; ++k) {
+    const int idx = threadIdx.x + 256 * k;  // quad idx of wpk: [tap][row][ch][q]
+    wreg[k] = wb.ld4(idx < NWQ ? idx * 16 : Buf::kOOB);
+  }
+  int t = t_lo + kx;
+  fetch(t, t < t_hi);
+#pragma unroll
+  for (int k = 0; k < NWL; ++k) {
+    const int idx = threadIdx.x + 256 * k;
+    const int q = idx & 3, ch = (idx >> 2) & 1, row = (idx >> 3) & 15, tap = idx >> 7;
+    if (idx < NWQ) *reinterpret_cast<float4*>(wts[ch] + (tap * 16 + row) * 16 + 4 * (q ^ ((row >> 1) & 3))) = wreg[k];
+  }
+  const int co = kgrp * 4;
+  const float4 al = *reinterpret_cast<const float4*>(alpha + co);
+  const float4 sh = *reinterpret_cast<const float4*>(shift + co);
+  const int mdl = wv / THI, mhl = wv - mdl * THI;  // the wave's input-grid row of the tile
+  const int woff = col * 16 + 4 * (kgrp ^ ((col >> 1) & 3));  // the lane's A fragment within a tap
+
+  commit();
+  __syncthreads();
+  for (; t < t_hi; t += per_xcd) {
+    const TileCoord c = coord(t);
+    const int tn = t + per_xcd;
+    const bool more = tn < t_hi;
+    const Fetch fn = fetch_of(tn, more);
+    const int md = c.md0 + mdl, mh = c.mh0 + mhl, mw = c.mw0 + col;
+    const bool ok = md < g.Di && mh < g.Hi && mw < g.Wi;
+    const size_t out_n = (size_t)c.n * g.Do * g.Ho * g.Wo * COUT;
+    const Buf sb(skip ? skip + out_n : nullptr, skip ? out_bytes : 0u), yb(y + out_n, out_bytes);
+    const int o0 = (((2 * md) * g.Ho + 2 * mh) * g.Wo + 2 * mw) * COUT + co;  // class 0 (floats)
+    int so[8];  // byte offset of the lane's 4 channels of each class's output voxel
+    float4 sk[8];  // the skip voxels
+#pragma unroll
+    for (int cls = 0; cls < 8; ++cls) {
+      const int rel = (((cls >> 2) * g.Ho + ((cls >> 1) & 1)) * g.Wo + (cls & 1)) * COUT;
+      so[cls] = ok ? (o0 + rel) * 4 : Buf::kOOB;
+    }
+    floatx4 acc[8];
+#pragma unroll
+    for (int cls = 0; cls < 8; ++cls) acc[cls] = floatx4{0.f, 0.f, 0.f, 0.f};
+    // deconv3d_lds_kernel's COUT == 16 epilogue of one class (a lane outside the volume stores nothing)
+    auto epilogue = [&](auto cc) {
+      constexpr int cls = decltype(cc)::value;
+      const float4 s = sk[cls];
+      float4 v;
+      v.x = s.x + act(fmaf(acc[cls][0], al.x, sh.x), g.lo);
+      v.y = s.y + act(fmaf(acc[cls][1], al.y, sh.y), g.lo);
+      v.z = s.z + act(fmaf(acc[cls][2], al.z, sh.z), g.lo);
+      v.w = s.w + act(fmaf(acc[cls][3], al.w, sh.w), g.lo);
+      yb.st4(v, so[cls]);
+    };
+    // 28 steps (chunk, tap pair). The A fragments of step s + 1 are read from LDS before step s's MFMAs
+    // (read right before their own MFMAs, every step opened with an exposed LDS round trip), and chunk 1's
+    // B fragments one per step during chunk 0's first 8.
+    VecN<PL> b[NCH][8], a[2][2];
+    auto bload = [&](int ch, int off) {
+      const int lvox = ((mdl + (off >> 2)) * LH + mhl + ((off >> 1) & 1)) * LW + col + (off & 1);
+      b[ch][off].load(tile[ch] + lvox * VST + 4 * (kgrp ^ ((lvox >> 1) & 3)));
+    };
+#pragma unroll
+    for (int off = 0; off < 8; ++off) bload(0, off);
+    a[0][0].load(wts[0] + deconv_stream_tap(0, 0).tap * 256 + woff);
+    a[0][1].load(wts[0] + deconv_stream_tap(1, 0).tap * 256 + woff);
+    __builtin_amdgcn_sched_barrier(0);
+    static_for(std::make_integer_sequence<int, 14 * NCH>{}, [&](auto sc) {
+      constexpr int s = decltype(sc)::value, ch = s / 14, i = s % 14;
+      constexpr DeconvTap t0 = deconv_stream_tap(0, i), t1 = deconv_stream_tap(1, i);
+      constexpr int s1 = s + 1, ch1 = s1 / 14, i1 = s1 % 14;
+      constexpr bool next = s1 < 14 * NCH, next0 = next && deconv_stream_tap(0, i1).cls >= 0;
+      if constexpr (next0) a[s1 & 1][0].load(wts[ch1] + deconv_stream_tap(0, i1).tap * 256 + woff);
+      if constexpr (next) a[s1 & 1][1].load(wts[ch1] + deconv_stream_tap(1, i1).tap * 256 + woff);
+      if constexpr (s < 8) bload(1, s);
+      // one global load per step of chunk 0: this tile's 8 skip voxels, then the next tile's staging loads
+      // (all 13 ahead of the MFMAs measured 39.6 -> 37.7 us at stage 3)
+      if constexpr (s < 8) sk[s] = sb.ld4(so[s]);
+      if constexpr (s >= 8 && s < 8 + NLD) fetch1(fn, s - 8);
+#pragma unroll
+      for (int j = 0; j < PL; ++j) {
+        if constexpr (t0.cls >= 0)
+          acc[t0.cls] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s & 1][0].v[j], b[ch][t0.off].v[j], acc[t0.cls], 0, 0, 0);
+        acc[t1.cls] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s & 1][1].v[j], b[ch][t1.off].v[j], acc[t1.cls], 0, 0, 0);
+      }
+      // the step's LDS reads first, then its MFMAs in the order written
+      __builtin_amdgcn_sched_group_barrier(0x100, (next0 ? 1 : 0) + (next ? 1 : 0) + (s < 8 ? 1 : 0), 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, t0.cls >= 0 ? 2 * PL : PL, 0);
+      // a class's epilogue one step behind its last MFMA: the stores leave spread over the second chunk's
+      // MFMAs (all 8 behind the tile measured 42.7 -> 39.6 us at stage 3)
+      if constexpr (ch == NCH - 1 && i >= 1 && deconv_class_done(i - 1) >= 0)
+        epilogue(std::integral_constant<int, deconv_class_done(i - 1)>{});
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    epilogue(std::integral_constant<int, deconv_class_done(13)>{});
+    __syncthreads();  // every wave is done with the tile
+    commit();         // (zeros behind the last tile)
+    __syncthreads();
+  }
+}
+
+// resident workgroups of the device for one persistent kernel (persistent_grid's cap)
+template <typename K>
+static int persistent_cap(K kernel) {
+  return persistent_grid(kernel, 1L << 40);
+}
+
+// deconv_dispatch takes this kernel from 1.5 tiles per resident workgroup on: measured faster than the
+// one-tile-per-workgroup kernel at 1.6 (stage 1: 29.8 -> 24.6 us) and 3.8 (stages 2 / 3); not measured below
+constexpr int kC16pMinTilesNum = 3, kC16pMinTilesDen = 2;
+
+// max_wgs > 0 bounds the grid below the device's residency (tests: a multi-tile walk on a small volume)
+template <int TDI, int THI>
+static int launch_deconv_c16p(const float* x, const float* w, const float* al, const float* sh, const float* skip,
+                              float* y, int B, const Geo& g, hipStream_t st, int max_wgs = 0) {
+  const long ntiles = (long)B * ((g.Di + TDI - 1) / TDI) * ((g.Hi + THI - 1) / THI) * ((g.Wi + 15) / 16);
+  long grid = persistent_grid(deconv3d_c16p_kernel<TDI, THI>, ntiles);
+  if (max_wgs > 0) grid = std::min<long>(grid, max_wgs);
+  hipLaunchKernelGGL((deconv3d_c16p_kernel<TDI, THI>), dim3((unsigned)grid), dim3(256), 0, st, x, w, al, sh, skip, y, g,
+                     (int)ntiles);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
 template <int CIN, int COUT, int TDI, int THI, int MBB>
 static int launch_deconv(const float* x, const float* w, const float* al, const float* sh, const float* skip,
                          float* y, int B, const Geo& g, hipStream_t st) {
@@ -1383,8 +1643,12 @@ static int conv_dispatch(const float* x, int B, int cin, int d, int h, int w, co
   return launch ? launch(x, wpk, al, sh, y, B, g, st) : TMVS_ERR_SHAPE;
 }
 
+// which kernel a layer that has a persistent form runs on: by its geometry (the product), or pinned
+enum class Route { kAuto, kGeneric, kPersistent };
+
 static int deconv_dispatch(const float* x, int B, int cin, int d, int h, int w, const float* wpk, const float* al,
-                           const float* sh, int cout, const float* skip, float* y, hipStream_t st, float lo = 0.f) {
+                           const float* sh, int cout, const float* skip, float* y, hipStream_t st, float lo = 0.f,
+                           Route route = Route::kAuto, int max_wgs = 0) {
   Geo g;
   g.lo = lo;
   g.Di = d;
@@ -1403,6 +1667,20 @@ static int deconv_dispatch(const float* x, int B, int cin, int d, int h, int w, 
     launch = even ? launch_deconv<32, 16, 2, 2, 1> : launch_deconv<32, 16, 1, 4, 1>;
   else if (cin == 16 && cout == 8)  // W-parity outputs packed into the 16 MFMA rows
     launch = even ? launch_deconv_c8<2, 2> : launch_deconv_c8<1, 4>;
+  if (cin == 32 && cout == 16 && route != Route::kGeneric) {
+    // conv9, persistent: it addresses one sample's input and output through buffers with 32-bit byte
+    // offsets, and is taken from kC16pMinTilesNum / kC16pMinTilesDen tiles per resident workgroup on
+    const bool fits = (long long)g.Do * g.Ho * g.Wo * cout * 4 < (1LL << 31);  // (the input is a quarter of it)
+    const int tdi = even ? 2 : 1, thi = even ? 2 : 4;
+    const long ntiles = (long)B * ((d + tdi - 1) / tdi) * ((h + thi - 1) / thi) * ((w + 15) / 16);
+    const int cap = even ? persistent_cap(deconv3d_c16p_kernel<2, 2>) : persistent_cap(deconv3d_c16p_kernel<1, 4>);
+    if (route == Route::kPersistent && !fits) return TMVS_ERR_SHAPE;
+    if (route == Route::kPersistent || (fits && ntiles * kC16pMinTilesDen >= (long)cap * kC16pMinTilesNum))
+      return even ? launch_deconv_c16p<2, 2>(x, wpk, al, sh, skip, y, B, g, st, max_wgs)
+                  : launch_deconv_c16p<1, 4>(x, wpk, al, sh, skip, y, B, g, st, max_wgs);
+  } else if (route == Route::kPersistent) {
+    return TMVS_ERR_SHAPE;  // no persistent form of this layer
+  }
   return launch ? launch(x, wpk, al, sh, skip, y, B, g, st) : TMVS_ERR_SHAPE;
 }
 
@@ -1425,6 +1703,25 @@ extern "C" int tmvs_deconv3d_bn_relu_add(const float* x, int batch, int cin, int
   if (!x || !wpk || !alpha || !shift || !skip || !y || batch <= 0 || d <= 0 || h <= 0 || w <= 0)
     return TMVS_ERR_ARG;
   return deconv_dispatch(x, batch, cin, d, h, w, wpk, alpha, shift, cout, skip, y, (hipStream_t)stream);
+}
+
+extern "C" int tmvs_deconv3d_bn_relu_add_generic(const float* x, int batch, int cin, int d, int h, int w,
+                                                 const float* wpk, const float* alpha, const float* shift, int cout,
+                                                 const float* skip, float* y, void* stream) {
+  if (!x || !wpk || !alpha || !shift || !skip || !y || batch <= 0 || d <= 0 || h <= 0 || w <= 0)
+    return TMVS_ERR_ARG;
+  return deconv_dispatch(x, batch, cin, d, h, w, wpk, alpha, shift, cout, skip, y, (hipStream_t)stream, 0.f,
+                         Route::kGeneric);
+}
+
+extern "C" int tmvs_deconv3d_bn_relu_add_persistent(const float* x, int batch, int cin, int d, int h, int w,
+                                                    const float* wpk, const float* alpha, const float* shift,
+                                                    int cout, const float* skip, float* y, int max_workgroups,
+                                                    void* stream) {
+  if (!x || !wpk || !alpha || !shift || !skip || !y || batch <= 0 || d <= 0 || h <= 0 || w <= 0 || max_workgroups < 0)
+    return TMVS_ERR_ARG;
+  return deconv_dispatch(x, batch, cin, d, h, w, wpk, alpha, shift, cout, skip, y, (hipStream_t)stream, 0.f,
+                         Route::kPersistent, max_workgroups);
 }
 
 // prob (8 -> 1) raw logits: one row per wave (two measured 42.3 -> 44.9 us at stage 1's D = 48, r16c)

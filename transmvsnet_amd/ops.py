@@ -334,9 +334,10 @@ def conv3d_bn_relu(x, wpk, alpha, shift, cout, stride, out=None):
     return y
 
 
-def deconv3d_bn_relu_add(x, wpk, alpha, shift, cout, skip, out=None):
+def deconv3d_bn_relu_add(x, wpk, alpha, shift, cout, skip, out=None, route=None, max_workgroups=0):
     """tmvs_deconv3d_bn_relu_add: skip + relu(conv_transpose * alpha + shift) at twice x's extents, written to
-    `out` (not skip itself) when given."""
+    `out` (not skip itself) when given. route "generic" / "persistent" pins the kernel
+    (tmvs_deconv3d_bn_relu_add_generic / _persistent, the latter with its grid bound max_workgroups)."""
     _layer_args("deconv3d_bn_relu_add", x, wpk, alpha, shift, cout)
     b, d, h, w, cin = x.shape
     shape = (b, 2 * d, 2 * h, 2 * w, cout)
@@ -346,9 +347,13 @@ def deconv3d_bn_relu_add(x, wpk, alpha, shift, cout, skip, out=None):
     _layer_like("deconv3d_bn_relu_add", "out", out, shape, x.device)
     _layer_no_alias("deconv3d_bn_relu_add", skip, out)
     y = torch.empty(shape, device=x.device) if out is None else out
-    with _Span("tmvs_deconv3d_bn_relu_add"):
-        _lib.check(_lib_h().tmvs_deconv3d_bn_relu_add(_ptr(x), b, cin, d, h, w, _ptr(wpk), _ptr(alpha), _ptr(shift),
-                                                      cout, _ptr(skip), _ptr(y), _stream()), "tmvs_deconv3d_bn_relu_add")
+    if route not in (None, "generic", "persistent"):
+        raise ValueError(f"deconv3d_bn_relu_add: unknown route {route!r}")
+    name = "tmvs_deconv3d_bn_relu_add" + ("_" + route if route else "")
+    tail = (int(max_workgroups), _stream()) if route == "persistent" else (_stream(),)
+    with _Span(name):
+        _lib.check(getattr(_lib_h(), name)(_ptr(x), b, cin, d, h, w, _ptr(wpk), _ptr(alpha), _ptr(shift), cout,
+                                           _ptr(skip), _ptr(y), *tail), name)
     return y
 
 
