@@ -84,7 +84,9 @@ int tmvs_stage_hypotheses(const float* depth_values, int n_values, const float* 
  *   sim_out      : [B][D][H][W]       wsum_out : [B][H][W] (PARTIAL only, else may be NULL)
  *   view_w_out   : [B][vw_total][H][W] written at vw_offset.. when view_w_in == NULL
  * Supported: C in {8,16,32}; D in {8,16,24,32,48,64}; 1 <= V <= TMVS_MAX_VIEWS;
- *            V*H*W*C*4 < 2^30 bytes per sample (32-bit buffer offsets); H, W <= 32766.      */
+ *            V*H*W*C*4 < 2^30 bytes per sample (32-bit buffer offsets); H, W <= 32766;
+ *            with view_w_in, H and W multiples of 2^vw_shift (else TMVS_ERR_SHAPE: the last
+ *            column / row would index past the weight map).                                 */
 #define TMVS_WARP_PARTIAL 1
 #define TMVS_WARP_ROT_PLAIN 2
 #define TMVS_WARP_BWD_PLANES 4 /* tmvs_warp_corr_backward: hyp[d] is one depth per plane (stage 1) */

@@ -112,6 +112,34 @@ def test_argument_validation_without_gpu(lib):
     assert lib.tmvs_fmt_forward_split(None, 0, None, 0, 0, 5, 216, 288, None, None, 0, None, None, None) == -1
 
 
+def test_warp_corr_shape_validation_without_gpu(lib):
+    """tmvs_warp_corr with given view weights reads them at (y >> vw_shift, x >> vw_shift) of an
+    [H >> vw_shift][W >> vw_shift] map, so a height or width that is no multiple of 2^vw_shift would
+    index column W >> vw_shift (and, on the last row, past the buffer): TMVS_ERR_SHAPE, as is a shift no
+    size can satisfy. tmvs_warp_corr_backward refuses planes with D > 64 likewise. Both before anything
+    is enqueued (the pointers are host memory that is never read; no device is needed to refuse)."""
+    ARG, SHAPE = -1, -2
+    backing = np.zeros(256, np.float32)
+    p = (backing.ctypes.data + 63) & ~63
+
+    def given(h, w, shift, c=8, d=8):
+        return lib.tmvs_warp_corr(p, p, p, p, p, shift, 0, 2, None, 1, 2, c, d, h, w, 0, p, None, None, None)
+
+    for h, w, shift in ((9, 28, 1), (8, 29, 1), (9, 29, 1), (10, 28, 2), (12, 30, 2), (4, 4, 3), (1, 8, 1),
+                        (16, 16, 15), (16, 16, 31), (16, 16, 32), (16, 16, 1 << 20)):
+        for c, d in ((8, 8), (16, 32), (32, 48)):
+            assert given(h, w, shift, c, d) == SHAPE, (h, w, shift, c, d)
+    assert given(8, 28, -1) == ARG
+    # the PARTIAL (view-sharded) form validates the same way
+    assert lib.tmvs_warp_corr(p, p, p, p, p, 1, 0, 2, None, 1, 2, 8, 8, 9, 29, _lib.WARP_PARTIAL, p, p, None,
+                              None) == SHAPE
+    # planes: D <= 64, refused before the workspace is cleared
+    big = 1 << 40
+    for c in (8, 16, 32):
+        assert lib.tmvs_warp_corr_backward(p, p, p, p, p, 2, c, 65, 5, 5, _lib.WARP_BWD_PLANES, p, big, p, p,
+                                           None) == SHAPE, c
+
+
 def test_training_primitive_validation_without_gpu(lib):
     """The training-only token and glue entry points (fmt_train / pathway_train / featurenet_train / loss):
     null pointers and non-positive sizes are TMVS_ERR_ARG (one pinned exception: tmvs_depth_metrics, see its

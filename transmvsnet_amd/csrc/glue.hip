@@ -5,6 +5,7 @@
 // and trilinearly resamples them; here each stage-resolution output evaluates the 1 (stage 3)
 // or 2x2 (stage 2) full-resolution samples it averages, in the reference's fp32 op order:
 //   cur  = fmaf(fmaf(x00,w0, x01*w1), h0, fmaf(x10,w0, x11*w1)*h1)   bilinear x2/x4 up-sampling
+//          (images with H + W <= 128: torch's small-output kernel, see upsample_at)
 //   hyp  = (cur - hr) + k * (((cur + hr) - (cur - hr)) / (nd - 1))
 //   out  = fmaf(fmaf(a,.5,b*.5), .5, fmaf(c,.5,d*.5)*.5)              trilinear 2x down (stage 2)
 // Regression: models/TransMVSNet.py:97-103,217-221, depth_wta models/module.py:474-482.
@@ -38,6 +39,13 @@ __device__ __forceinline__ float upsample_at(const float* __restrict__ prev, int
   const LinAxis ax = lin_axis(x, pw, W);
   const float* r0 = prev + (size_t)ay.i0 * pw;
   const float* r1 = prev + (size_t)ay.i1 * pw;
+  // torch's CPU upsample_bilinear2d takes another kernel for small outputs (H + W <= 128, its channels-last
+  // form, which a one-channel map satisfies): the 4 taps times the products of the axis weights, summed as
+  // fmaf(x11,w11, fmaf(x10,w10, fmaf(x00,w00, x01*w01))). Up to 2 ulp from the separable form below.
+  if (H + W <= 128) {
+    const float w00 = ay.l0 * ax.l0, w01 = ay.l0 * ax.l1, w10 = ay.l1 * ax.l0, w11 = ay.l1 * ax.l1;
+    return fmaf(r1[ax.i1], w11, fmaf(r1[ax.i0], w10, fmaf(r0[ax.i0], w00, r0[ax.i1] * w01)));
+  }
   const float t0 = fmaf(r0[ax.i0], ax.l0, r0[ax.i1] * ax.l1);
   const float t1 = fmaf(r1[ax.i0], ax.l0, r1[ax.i1] * ax.l1);
   return fmaf(t0, ay.l0, t1 * ay.l1);

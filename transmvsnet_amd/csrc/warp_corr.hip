@@ -1067,6 +1067,10 @@ extern "C" int tmvs_warp_corr(const float* ref_fea, const float* src_fea, const 
   // the kernel addresses one sample's source views with 32-bit byte offsets (< 2^30)
   if ((long long)n_src * height * width * channels * 4 >= (1LL << 30)) return TMVS_ERR_SHAPE;
   if (width > 32766 || height > 32766) return TMVS_ERR_SHAPE;
+  // given weights are read at (y >> vw_shift, x >> vw_shift) of an [H >> vw_shift][W >> vw_shift] map: a
+  // remainder would put the last column / row at index W >> vw_shift / H >> vw_shift, past the map
+  if (!pw && (vw_shift > 14 || (height & ((1 << vw_shift) - 1)) || (width & ((1 << vw_shift) - 1))))
+    return TMVS_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const size_t HW = (size_t)height * width;
   for (int b = 0; b < batch; ++b) {
@@ -1154,6 +1158,8 @@ extern "C" int tmvs_warp_corr_backward(const float* ref_fea, const float* src_fe
   if (n_src <= 0 || n_src > TMVS_MAX_VIEWS || ndepth <= 0 || height <= 0 || width <= 0) return TMVS_ERR_ARG;
   if (width > 32766 || height > 32766) return TMVS_ERR_SHAPE;
   if (workspace_bytes < tmvs_warp_corr_backward_workspace(n_src, channels, height, width, ndepth)) return TMVS_ERR_ARG;
+  const bool planes = (flags & TMVS_WARP_BWD_PLANES) != 0;
+  if (planes && ndepth > kPlanesMaxD) return TMVS_ERR_SHAPE;  // before anything is enqueued
   hipStream_t st = (hipStream_t)stream;
   WarpArgs a = {};
   a.rot_plain = (flags & TMVS_WARP_ROT_PLAIN) ? 1 : 0;
@@ -1163,7 +1169,7 @@ extern "C" int tmvs_warp_corr_backward(const float* ref_fea, const float* src_fe
   unsigned long long* fix = (unsigned long long*)workspace;
   int* ovf = (int*)((char*)workspace + (size_t)n * sizeof(unsigned long long));
   unsigned* absmax = (unsigned*)(ovf + 1);
-  if ((flags & TMVS_WARP_BWD_PLANES) ? hipMemsetAsync(ovf, 0, 3 * sizeof(int), st) != hipSuccess
+  if (planes ? hipMemsetAsync(ovf, 0, 3 * sizeof(int), st) != hipSuccess
                                       : hipMemsetAsync(workspace, 0, (size_t)n * sizeof(unsigned long long) + 3 * sizeof(int),
                                                        st) != hipSuccess)
     return TMVS_ERR_HIP;
@@ -1177,8 +1183,6 @@ extern "C" int tmvs_warp_corr_backward(const float* ref_fea, const float* src_fe
   const int dchunk = bwd_dchunk(ndepth), nch = (ndepth + dchunk - 1) / dchunk;
   float* part = (float*)((char*)workspace + (size_t)n * sizeof(unsigned long long) + 256);
   const dim3 grid((HW + 255) / 256, n_src, nch);
-  const bool planes = (flags & TMVS_WARP_BWD_PLANES) != 0;
-  if (planes && ndepth > kPlanesMaxD) return TMVS_ERR_SHAPE;
   const dim3 pgrid((HW + 63) / 64, n_src);
 #define TMVS_BWD_CASE(CC)                                                                                              \
   case CC:                                                                                                             \

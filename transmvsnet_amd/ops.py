@@ -844,12 +844,15 @@ def bn_relu_backward_grouped(dy, z, mean, var, gamma, beta, eps):
     return dz, dg, db
 
 
-def warp_corr_backward(ref_nhwc, src_nhwc, proj12, hyp, dsim, rot_order="auto", planes=False):
+def warp_corr_backward(ref_nhwc, src_nhwc, proj12, hyp, dsim, rot_order="auto", planes=False, dref_out=None,
+                       dsrc_out=None):
     """tmvs_warp_corr_backward: one sample, ref [H,W,C], src [V,H,W,C] NHWC, proj12 HOST [V,12],
     hyp [D,H,W], dsim [V,D,H,W] -> (dref [H,W,C], dsrc [V,H,W,C], flag tensor [1] int32: bit 0 a
     non-finite dsim / ref, bit 1 non-planar hyp under planes=True). planes=True (TMVS_WARP_BWD_PLANES:
-    hyp[d] is one depth per plane, stage 1) gathers dsrc per source texel instead of scattering it."""
-    for t, n in ((ref_nhwc, "ref"), (src_nhwc, "src"), (hyp, "hyp"), (dsim, "dsim")):
+    hyp[d] is one depth per plane, stage 1) gathers dsrc per source texel instead of scattering it.
+    dref_out / dsrc_out: caller-provided contiguous outputs of those shapes."""
+    for t, n in ((ref_nhwc, "ref"), (src_nhwc, "src"), (hyp, "hyp"), (dsim, "dsim"), (dref_out, "dref_out"),
+                 (dsrc_out, "dsrc_out")):
         _dev(t, n)
     v, h, w, c = src_nhwc.shape
     d = hyp.shape[0]
@@ -858,8 +861,12 @@ def warp_corr_backward(ref_nhwc, src_nhwc, proj12, hyp, dsim, rot_order="auto", 
     proj = np.ascontiguousarray(proj12, np.float32).reshape(v, 12)
     nbytes = _lib_h().tmvs_warp_corr_backward_workspace(v, c, h, w, hyp.shape[0])
     ws = torch.empty(nbytes // 4 + 64, device=hyp.device)
-    dref = torch.empty_like(ref_nhwc)
-    dsrc = torch.empty_like(src_nhwc)
+    dref = torch.empty_like(ref_nhwc) if dref_out is None else dref_out
+    dsrc = torch.empty_like(src_nhwc) if dsrc_out is None else dsrc_out
+    if tuple(dref.shape) != (h, w, c) or not dref.is_contiguous():
+        raise ValueError(f"dref_out must be a contiguous [{h},{w},{c}] tensor")
+    if tuple(dsrc.shape) != (v, h, w, c) or not dsrc.is_contiguous():
+        raise ValueError(f"dsrc_out must be a contiguous [{v},{h},{w},{c}] tensor")
     with _Span("tmvs_warp_corr_backward"):
         _lib.check(_lib_h().tmvs_warp_corr_backward(_ptr(ref_nhwc), _ptr(src_nhwc), proj.ctypes.data, _ptr(hyp), _ptr(dsim),
                                                     v, c, d, h, w,
