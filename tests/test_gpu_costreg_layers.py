@@ -9,7 +9,9 @@ the VALU kernels, and the 256-thread block edge of softmax / WTA.
   conv1  8 -> 16 s2   conv3d_s2c8_tile_kernel<2, 2>   persistent
   conv2  16 -> 16 s1  conv3d_c16_kernel<2, 4>         persistent
   conv3 .. conv6      conv3d_lds_kernel, straight / KDSKIP (output depth <= 2) / TAPOUT (conv5)
-  conv7, conv9        deconv3d_lds_kernel, 2 x 2 input tiles (even input depth) / 1 x 4 (odd)
+  conv7 64 -> 32      deconv3d_lds_kernel, 2 x 2 input tiles (even input depth) / 1 x 4 (odd)
+  conv9 32 -> 16      deconv3d_lds_kernel at these shapes (below 1.5 tiles per resident workgroup); from there on
+                      deconv3d_c16p_kernel, persistent (tests/test_gpu_costreg_persistent.py)
   conv11 16 -> 8      deconv3d_c8_kernel, 2 x 2 / 1 x 4, persistent
   conv0 1 -> 8, prob 8 -> 1   conv0_kernel / prob_kernel (VALU), prob_wta_rows_kernel through costregnet_wta
 

@@ -12,9 +12,10 @@
 //   B (4 x 16) = input     [k][voxel]  lane l: k = l>>4,   voxel = l&15
 //   D (16 x16)                          lane l: cout = 4*(l>>4)+r, voxel = l&15  -> one float4
 //                                       store of 4 consecutive channels (NDHWC) per lane.
-// K runs over (tap, channel): per tap and CK-channel chunk a lane loads CK/4 consecutive
-// channels of one voxel (float4/float2) and issues CK/4 MFMAs, MFMA j taking channel
-// chunk + (l>>4)*(CK/4) + j in both operands. A "task" (one wave) is NBW rows of 16 output
+// K runs over (tap, channel): per tap and 16-channel chunk a lane loads 4 consecutive
+// channels of one voxel (one float4) and issues 4 MFMAs, MFMA j taking channel
+// chunk + (l>>4)*4 + j in both operands (conv1's 8 input channels: tap pairs, see its kernel).
+// A "task" (one wave) is NBW rows of 16 output
 // voxels x MBW blocks of 16 output channels; the 4 waves of a workgroup share the rows and
 // split the output channels, so their input taps hit in L1.
 // The transposed convs (ConvTranspose3d k3 s2 p1 op1) use the sub-pixel decomposition: a
@@ -28,10 +29,8 @@ namespace tmvs {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-template <int N>
-struct VecN;
-template <>
-struct VecN<4> {
+// 4 consecutive channels of one voxel (B) or weight row (A): the operands of 4 MFMAs
+struct Vec4 {
   float v[4];
   __device__ __forceinline__ void load(const float* p) {
     const float4 t = *reinterpret_cast<const float4*>(p);
@@ -41,16 +40,6 @@ struct VecN<4> {
     v[3] = t.w;
   }
   __device__ __forceinline__ void zero() { v[0] = v[1] = v[2] = v[3] = 0.f; }
-};
-template <>
-struct VecN<2> {
-  float v[2];
-  __device__ __forceinline__ void load(const float* p) {
-    const float2 t = *reinterpret_cast<const float2*>(p);
-    v[0] = t.x;
-    v[1] = t.y;
-  }
-  __device__ __forceinline__ void zero() { v[0] = v[1] = 0.f; }
 };
 
 // Range-checked raw buffer over one tensor: a lane whose 32-bit byte offset is out of range reads
@@ -71,36 +60,124 @@ struct Buf {
     const uintx4 u{__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
     __builtin_amdgcn_raw_buffer_store_b128(u, r, voff, 0, 0);
   }
-  __device__ __forceinline__ float2 ld2(int voff, int soff = 0) const {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-    return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
-  }
 };
-template <int N>
-__device__ __forceinline__ void buf_load(VecN<N>& d, const Buf& b, int voff, int soff = 0);
-template <>
-__device__ __forceinline__ void buf_load<4>(VecN<4>& d, const Buf& b, int voff, int soff) {
+__device__ __forceinline__ void buf_load(Vec4& d, const Buf& b, int voff, int soff = 0) {
   const float4 t = b.ld4(voff, soff);
   d.v[0] = t.x, d.v[1] = t.y, d.v[2] = t.z, d.v[3] = t.w;
-}
-template <>
-__device__ __forceinline__ void buf_load<2>(VecN<2>& d, const Buf& b, int voff, int soff) {
-  const float2 t = b.ld2(voff, soff);
-  d.v[0] = t.x, d.v[1] = t.y;
 }
 
 struct Geo {
   int Di, Hi, Wi;  // input dims
   int Do, Ho, Wo;  // output dims
   float lo;        // epilogue floor: 0 = ReLU, -inf = none
+  static Geo conv(int d, int h, int w, int stride, float lo) {  // k3 p1
+    return stride == 1 ? Geo{d, h, w, d, h, w, lo} : Geo{d, h, w, (d - 1) / 2 + 1, (h - 1) / 2 + 1, (w - 1) / 2 + 1, lo};
+  }
+  static Geo deconv(int d, int h, int w, float lo) { return Geo{d, h, w, 2 * d, 2 * h, 2 * w, lo}; }  // k3 s2 p1 op1
 };
 
 __device__ __forceinline__ float act(float v, float lo) { return v > lo ? v : lo; }
 
+// ---------------------------------------------------------------- shared by the MFMA kernels
+// the epilogue of one D fragment: eval-mode BN and the activation floor on a lane's 4 channels
+__device__ __forceinline__ float4 bn_act4(floatx4 acc, float4 alpha, float4 shift, float lo) {
+  return make_float4(act(fmaf(acc[0], alpha.x, shift.x), lo), act(fmaf(acc[1], alpha.y, shift.y), lo),
+                     act(fmaf(acc[2], alpha.z, shift.z), lo), act(fmaf(acc[3], alpha.w, shift.w), lo));
+}
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// The LDS format of every 16-channel tile and weight block: float offset of channel quad q (4 floats,
+// one ds_read_b128) of voxel / weight row `vox`. Voxel stride 16 floats and the quad swizzle are chosen
+// so the 4 lane groups of every ds_read_b128 are bank-conflict free (exhaustive search over the gfx950
+// b128 lane grouping); stride-2 reads included (conv3's instance). Two places spell the same
+// layout out, for the reason given there: conv3d_lds_kernel and conv11's 8-row weight staging.
+__device__ __forceinline__ int swz16(int vox, int q) { return vox * 16 + 4 * (q ^ ((vox >> 1) & 3)); }
+template <typename T>  // the quad's address in the tile / weight block at `base`
+__device__ __forceinline__ T* swz16(T* base, int vox, int q) {
+  return base + vox * 16 + 4 * (q ^ ((vox >> 1) & 3));
+}
+
+// Weights [27 taps][COUT][CIN] -> LDS [27][16][16] for output rows row0 .. row0 + 15 and input channels
+// ch0 .. ch0 + 15, the rows quad-swizzled like the tile's voxels so the A-fragment ds_read_b128 is
+// bank-conflict free. 256 threads.
+template <int COUT, int CIN>
+__device__ __forceinline__ void stage_weights16(float* wts, const float* __restrict__ wpk, int row0, int ch0) {
+  for (int idx = threadIdx.x; idx < 27 * 16 * 4; idx += 256) {
+    const int q = idx & 3, row = (idx >> 2) & 15, tap = idx >> 6;
+    const float4 v = *reinterpret_cast<const float4*>(wpk + ((size_t)tap * COUT + row0 + row) * CIN + ch0 + 4 * q);
+    *reinterpret_cast<float4*>(swz16(wts + tap * 256, row, q)) = v;
+  }
+}
+
+// Tile t of a volume cut into nds x nhs x nws tiles of TD x TH x 16 voxels per sample, w fastest
+struct TileCoord {
+  int n, d0, h0, w0;
+};
+__device__ __forceinline__ TileCoord tile_coord(int t, int nws, int nhs, int nds, int TH, int TD) {
+  TileCoord c;
+  c.w0 = (t % nws) * 16;
+  t /= nws;
+  c.h0 = (t % nhs) * TH;
+  t /= nhs;
+  c.d0 = (t % nds) * TD;
+  c.n = t / nds;
+  return c;
+}
+
+// A persistent workgroup's share of the ntiles tiles: first(), first() + step, ... below end.
+// XCD-contiguous ranges (an XCD's workgroups share one L2: neighbouring tiles share their halo voxels):
+// workgroup b runs on XCD b % 8 (round-robin dispatch), so XCD x's workgroups deal out tiles
+// [ntiles x / 8, ntiles (x + 1) / 8) among themselves.
+struct TileRange {
+  int lo, k, end, step;  // the XCD's first tile, the workgroup's place among the XCD's, the XCD's end, its workgroups
+  __device__ __forceinline__ explicit TileRange(int ntiles) {
+    const int nxcd = gridDim.x >= 8 ? 8 : 1, per_xcd = gridDim.x / nxcd;
+    const int xcd = blockIdx.x % nxcd, kx = blockIdx.x / nxcd;
+    const int t_lo = (int)((long)ntiles * xcd / nxcd), t_hi = (int)((long)ntiles * (xcd + 1) / nxcd);
+    lo = t_lo, k = kx, end = t_hi, step = per_xcd;
+  }
+  __device__ __forceinline__ bool idle() const { return k >= step; }  // grid not a multiple of 8: the remainder idles
+  __device__ __forceinline__ int first() const { return lo + k; }
+};
+
+// ConvTranspose3d k3 s2 p1 op1, one dimension: output o = 2i - 1 + k, so an even output (parity 0) has the
+// one tap (k = 1, i = o/2) and an odd one (parity 1) two: t = 0 -> (k = 0, i = o/2 + 1), t = 1 -> (k = 2, i = o/2).
+struct ParityTap {
+  int k, off;  // kernel index, input offset from o/2
+};
+constexpr ParityTap parity_tap(int p, int t) { return ParityTap{p ? (t ? 2 : 0) : 1, (p && !t) ? 1 : 0}; }
+// A parity class cls = 4 pd + 2 ph + pw (16 outputs with one parity per dimension) has (1 + pd)(1 + ph)(1 + pw) taps
+struct DeconvTap {
+  int cls, tap, off;  // parity class, weight tap, input voxel offset (bit 2: depth, 1: row, 0: column)
+};
+constexpr int deconv_class_taps(int cls) { return (1 + (cls >> 2)) * (1 + ((cls >> 1) & 1)) * (1 + (cls & 1)); }
+// tap i of class cls, in (td, th, tw) order: the K order of every transposed kernel
+constexpr DeconvTap deconv_class_tap(int cls, int i) {
+  const int pd = cls >> 2, ph = (cls >> 1) & 1, pw = cls & 1;
+  const ParityTap d = parity_tap(pd, i / ((1 + ph) * (1 + pw))), h = parity_tap(ph, i / (1 + pw) % (1 + ph)),
+                  w = parity_tap(pw, i % (1 + pw));
+  return DeconvTap{cls, d.k * 9 + h.k * 3 + w.k, d.off * 4 + h.off * 2 + w.off};
+}
+constexpr bool deconv_taps_cover() {  // 27 distinct taps over the 8 classes, 1, 2, 2, 4, 2, 4, 4, 8 per class
+  constexpr int want[8] = {1, 2, 2, 4, 2, 4, 4, 8};
+  bool seen[27] = {};
+  int n = 0;
+  for (int cls = 0; cls < 8; ++cls) {
+    if (deconv_class_taps(cls) != want[cls]) return false;
+    for (int i = 0; i < deconv_class_taps(cls); ++i, ++n) {
+      const int tap = deconv_class_tap(cls, i).tap;
+      if (tap < 0 || tap >= 27 || seen[tap]) return false;
+      seen[tap] = true;
+    }
+  }
+  return n == 27;
+}
+static_assert(deconv_taps_cover(), "the parity rule enumerates the 27 taps once");
+
 // ---------------------------------------------------------------- conv3d k3 p1, stride S
 // Workgroup tile: 16 output voxels along w x TH rows x TD depth slices, MBB blocks of 16
-// output channels. Per CK-channel chunk the input tile (+halo) is staged once into LDS
-// (voxel stride CK+4 floats: the 16 lanes of a row hit distinct banks), then each wave runs
+// output channels. Per 16-channel chunk the input tile (+halo) is staged once into LDS
+// (swz16's layout: the 16 lanes of a row hit distinct banks), then each wave runs
 // its NBW = TD*TH/4 rows through the 27 taps: A (weights) from global/L2, requested two taps
 // ahead, B from LDS. The next chunk's tile is fetched into registers during the current
 // chunk's MFMAs.
@@ -114,20 +191,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLdsWavesPe
                                                          const float* __restrict__ alpha,
                                                          const float* __restrict__ shift, float* __restrict__ y,
                                                          Geo g) {
-  constexpr int CK = CIN < 16 ? CIN : 16;
-  constexpr int PL = CK / 4;
-  constexpr int MB = (COUT + 15) / 16;
+  constexpr int CK = 16, PL = 4;  // channels per chunk, per lane (one float4, 4 MFMAs)
+  constexpr int MB = COUT / 16;
   constexpr int MG = MB / MBB;
+  static_assert(CIN % 16 == 0 && COUT % 16 == 0, "16-channel input chunks, 16-channel output blocks");
   // WS: the 4 waves are WS block groups x 4/WS row groups; a wave runs NBW rows x MBW blocks (WS = 1:
   // every wave all MBB blocks of TD*TH/4 rows -- the 4 waves then request identical weight fragments)
   static_assert(WS == 1 || WS == 2 || WS == 4, "WS");
   static_assert(MBB % WS == 0 && (TD * TH * WS) % 4 == 0, "wave split");
   constexpr int NBW = TD * TH * WS / 4, MBW = MBB / WS;
   constexpr int LW = 15 * S + 3, LH = (TH - 1) * S + 3, LD = (TD - 1) * S + 3;
-  // voxel stride / quad swizzle chosen so the 4 lane groups of every ds_read_b128 are
-  // bank-conflict free (exhaustive search over the gfx950 b128 lane grouping)
-  constexpr bool SWZ = (CK == 16);  // (stride 2 included: conv3's instance)
-  constexpr int VST = SWZ ? 16 : CK + 4;
+  // This kernel spells out swz16's layout (commit_from, bload_at), its tile decode and the weight loads' dead
+  // `co < COUT` select as before: through the helpers, or without the select, every instance compiled to
+  // another instruction stream, and conv4's measured 0.3 us slower (profiles/costreg_scaffold_resources.md).
+  constexpr int VST = 16;  // (stride 2 included: conv3's instance)
   constexpr int NVOX = LD * LH * LW;
   static_assert(MB % MBB == 0, "tile");
   static_assert(!TAPOUT || (TD == 1 && !KDSKIP), "TAPOUT: one output slice per workgroup, its own kd skip");
@@ -182,7 +259,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLdsWavesPe
     for (int k = 0; k < NLD; ++k) {
       const int idx = threadIdx.x + 256 * k;
       const int vox = idx / PL, q = idx - vox * PL;
-      const int qs = SWZ ? (q ^ ((vox >> 1) & 3)) : q;
+      const int qs = q ^ ((vox >> 1) & 3);
       if (idx < NVOX * PL) *reinterpret_cast<float4*>(base + vox * VST + 4 * qs) = src[k];
     }
   };
@@ -202,28 +279,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLdsWavesPe
   }
   // A fragments (chunk ch, tap) from global/L2, requested two taps ahead of their MFMAs; the
   // chunk's last two taps request the next chunk's first two
-  auto wload = [&](int ch, int tap, VecN<PL>(&a)[MBW]) {
+  auto wload = [&](int ch, int tap, Vec4(&a)[MBW]) {
 #pragma unroll
     for (int m = 0; m < MBW; ++m) {
       const int co = (mb0 + m) * 16 + col;  // channels >= COUT read zeros
       buf_load(a[m], wb, (co < COUT ? co * CIN + kgrp * PL : Buf::kOOB / 4) * 4, (tap * COUT * CIN + ch * CK) * 4);
     }
   };
-  VecN<PL> aw[3][MBW];
+  Vec4 aw[3][MBW];
   // B fragments of one tap from the LDS tile
-  auto bload_at = [&](const float* base, int kd, int kh, int kw, VecN<PL>(&b)[NBW]) {
+  auto bload_at = [&](const float* base, int kd, int kh, int kw, Vec4(&b)[NBW]) {
 #pragma unroll
     for (int r = 0; r < NBW; ++r) {
       const int rr = rg * NBW + r;
       const int odl = rr / TH, ohl = rr - odl * TH;
       const int lvox = ((odl * S + kd) * LH + ohl * S + kh) * LW + col * S + kw;
-      const int qs = SWZ ? (kgrp ^ ((lvox >> 1) & 3)) : kgrp;
+      const int qs = kgrp ^ ((lvox >> 1) & 3);
       b[r].load(base + lvox * VST + qs * PL);
     }
   };
-  auto bload = [&](int kd, int kh, int kw, VecN<PL>(&b)[NBW]) { bload_at(tile, kd, kh, kw, b); };
+  auto bload = [&](int kd, int kh, int kw, Vec4(&b)[NBW]) { bload_at(tile, kd, kh, kw, b); };
   // one tap: NBW x MBB x PL MFMAs on fragments already in registers
-  auto tap_mfma = [&](const VecN<PL>* a, const VecN<PL>* b) {
+  auto tap_mfma = [&](const Vec4* a, const Vec4* b) {
 #pragma unroll
     for (int j = 0; j < PL; ++j)
 #pragma unroll
@@ -240,7 +317,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLdsWavesPe
   };
   // B of tap t + 1 is read from LDS before tap t's MFMAs (read right before its own MFMAs its
   // latency sat between every tap's MFMA groups)
-  VecN<PL> bw[2][NBW];
+  Vec4 bw[2][NBW];
   if constexpr (TAPOUT) {
     // all chunks staged (every chunk's loads in flight before the first commit), then per kept kd slice
     // 9 taps x NCH chunks as one step sequence with the same two-step weight / one-step B lookahead
@@ -254,8 +331,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLdsWavesPe
     const int klo = id_base < 0 ? -id_base : 0;
     const int khi = od0 >= g.Do ? -1 : (g.Di - 1 - id_base < 2 ? g.Di - 1 - id_base : 2);
     constexpr int NS = 9 * NCH;  // steps per slice; a multiple of 3, so the weight ring lines up across slices
-    auto wstep = [&](int kd, int s, VecN<PL>(&a)[MBW]) { wload(s % NCH, kd * 9 + s / NCH, a); };
-    auto bstep = [&](int kd, int s, VecN<PL>(&b)[NBW]) {
+    auto wstep = [&](int kd, int s, Vec4(&a)[MBW]) { wload(s % NCH, kd * 9 + s / NCH, a); };
+    auto bstep = [&](int kd, int s, Vec4(&b)[NBW]) {
       const int t9 = s / NCH;
       bload_at(tile + (s % NCH) * NVOX * VST, kd, t9 / 3, t9 % 3, b);
     };
@@ -346,7 +423,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLdsWavesPe
 #pragma unroll
   for (int m = 0; m < MBW; ++m) {
     const int co = (mb0 + m) * 16 + kgrp * 4;
-    if (co >= COUT) continue;
     const float4 al = *reinterpret_cast<const float4*>(alpha + co);
     const float4 sh = *reinterpret_cast<const float4*>(shift + co);
 #pragma unroll
@@ -354,69 +430,50 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLdsWavesPe
       const int rr = rg * NBW + r;
       const int od = od0 + rr / TH, oh = oh0 + rr % TH;
       if (od >= g.Do || oh >= g.Ho) continue;
-      float4 o;
-      o.x = act(fmaf(acc[r][m][0], al.x, sh.x), g.lo);
-      o.y = act(fmaf(acc[r][m][1], al.y, sh.y), g.lo);
-      o.z = act(fmaf(acc[r][m][2], al.z, sh.z), g.lo);
-      o.w = act(fmaf(acc[r][m][3], al.w, sh.w), g.lo);
-      *reinterpret_cast<float4*>(y + (out_n + ((size_t)od * g.Ho + oh) * g.Wo + ow) * COUT + co) = o;
+      *reinterpret_cast<float4*>(y + (out_n + ((size_t)od * g.Ho + oh) * g.Wo + ow) * COUT + co) =
+          bn_act4(acc[r][m], al, sh, g.lo);
     }
   }
 }
 
 // ---------------------------------------------------------------- ConvTranspose3d k3 s2 p1 op1
-// output o = 2i - 1 + k: parity 0 -> (k=1, i=o/2); parity 1 -> (k=0, i=o/2+1), (k=2, i=o/2).
 // Workgroup tile in input-grid coordinates: 16 columns x THI rows x TDI slices (outputs
-// 32 x 2THI x 2TDI). Each wave owns TDI*THI/4 input-grid rows and all 8 output parity
-// classes of them (a class = 16 outputs with one parity per dimension = one tap set of
-// 1, 2, 4 or 8 taps), so the waves carry equal work. Input tile (+1 halo) staged in LDS.
-template <int CIN, int COUT, int TDI, int THI, int MBB>
+// 32 x 2THI x 2TDI), one block of 16 output channels. Each wave owns TDI*THI/4 input-grid rows and
+// all 8 output parity classes of them (a class = one tap set of 1, 2, 4 or 8 taps, deconv_class_tap),
+// so the waves carry equal work. Input tile (+1 halo) staged in LDS.
+template <int CIN, int COUT, int TDI, int THI>
 __global__ __launch_bounds__(256) void deconv3d_lds_kernel(const float* __restrict__ x,
                                                            const float* __restrict__ wpk,
                                                            const float* __restrict__ alpha,
                                                            const float* __restrict__ shift,
                                                            const float* __restrict__ skip, float* __restrict__ y,
                                                            Geo g) {
-  constexpr int CK = CIN < 16 ? CIN : 16;
-  constexpr int PL = CK / 4;
-  constexpr int MB = (COUT + 15) / 16;
-  constexpr int MG = MB / MBB;
+  constexpr int CK = 16, PL = 4;  // channels per chunk, per lane (one float4, 4 MFMAs)
+  constexpr int MG = COUT / 16;
   constexpr int NBW = TDI * THI / 4;
   constexpr int LW = 17, LH = THI + 1, LD = TDI + 1;
-  constexpr bool SWZ = (CK == 16);  // conflict-free ds_read_b128 (see conv3d_lds_kernel)
-  constexpr int VST = SWZ ? 16 : CK + 4;
   constexpr int NVOX = LD * LH * LW;
-  static_assert(MB % MBB == 0 && (TDI * THI) % 4 == 0, "tile");
-  static_assert(CK == 16 && MBB == 1, "LDS weight staging assumes 16-channel chunks, one 16-row block");
-  // weights of the current channel chunk: [27 taps][RM rows][16 ch], quad-swizzled like the
-  // tile so the A-fragment ds_read_b128 is bank-conflict free (a per-tap global load right
+  static_assert((TDI * THI) % 4 == 0, "tile");
+  static_assert(CIN % 16 == 0 && COUT % 16 == 0, "16-channel input chunks, 16-channel output blocks");
+  // weights of the current channel chunk in LDS (stage_weights16; a per-tap global load right
   // before its MFMAs exposed a full memory latency per tap: MFMA busy 35 %)
-  constexpr int RM = COUT < 16 ? COUT : 16;
-  __shared__ __attribute__((aligned(16))) float tile[NVOX * VST];
-  __shared__ __attribute__((aligned(16))) float wts[27 * RM * 16];
+  __shared__ __attribute__((aligned(16))) float tile[NVOX * 16];
+  __shared__ __attribute__((aligned(16))) float wts[27 * 16 * 16];
 
   const int nws = (g.Wi + 15) / 16, nhs = (g.Hi + THI - 1) / THI, nds = (g.Di + TDI - 1) / TDI;
-  int t = xcd_remap(blockIdx.x, gridDim.x);  // contiguous tiles per XCD: halos share an L2
-  const int mg = t % MG;
-  t /= MG;
-  const int ws = t % nws;
-  t /= nws;
-  const int hs = t % nhs;
-  t /= nhs;
-  const int ds = t % nds;
-  const int n = t / nds;
-  const int mw0 = ws * 16, mh0 = hs * THI, md0 = ds * TDI;
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);  // contiguous tiles per XCD: halos share an L2
+  const int mg = wg % MG;
+  const TileCoord c = tile_coord(wg / MG, nws, nhs, nds, THI, TDI);
+  const int n = c.n, mw0 = c.w0, mh0 = c.h0, md0 = c.d0;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int col = lane & 15, kgrp = lane >> 4;
   const size_t in_n = (size_t)n * g.Di * g.Hi * g.Wi;
 
-  floatx4 acc[NBW][8][MBB];
+  floatx4 acc[NBW][8];
 #pragma unroll
   for (int r = 0; r < NBW; ++r)
 #pragma unroll
-    for (int c = 0; c < 8; ++c)
-#pragma unroll
-      for (int m = 0; m < MBB; ++m) acc[r][c][m] = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int cls = 0; cls < 8; ++cls) acc[r][cls] = floatx4{0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll 1
   for (int ch = 0; ch < CIN / CK; ++ch) {
@@ -428,118 +485,48 @@ __global__ __launch_bounds__(256) void deconv3d_lds_kernel(const float* __restri
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (iw < g.Wi && ih < g.Hi && id < g.Di)
         v = *reinterpret_cast<const float4*>(x + (in_n + ((size_t)id * g.Hi + ih) * g.Wi + iw) * CIN + ch * CK + 4 * q);
-      const int qs = SWZ ? (q ^ ((vox >> 1) & 3)) : q;
-      *reinterpret_cast<float4*>(tile + vox * VST + 4 * qs) = v;
+      *reinterpret_cast<float4*>(swz16(tile, vox, q)) = v;
     }
-    for (int idx = threadIdx.x; idx < 27 * RM * 4; idx += 256) {
-      const int q = idx & 3, row = (idx >> 2) % RM, tap = (idx >> 2) / RM;
-      const float4 v = *reinterpret_cast<const float4*>(wpk + ((size_t)tap * COUT + mg * 16 + row) * CIN + ch * CK + 4 * q);
-      *reinterpret_cast<float4*>(wts + (tap * RM + row) * 16 + 4 * (q ^ ((row >> 1) & 3))) = v;
-    }
+    stage_weights16<COUT, CIN>(wts, wpk, mg * 16, ch * CK);
     __syncthreads();
 #pragma unroll
     for (int cls = 0; cls < 8; ++cls) {
-      const int pd = cls >> 2, ph = (cls >> 1) & 1, pw = cls & 1;
 #pragma unroll
-      for (int td = 0; td < 1 + pd; ++td)
+      for (int i = 0; i < deconv_class_taps(cls); ++i) {
+        const DeconvTap t = deconv_class_tap(cls, i);
+        Vec4 a;
+        a.load(swz16(wts + t.tap * 256, col, kgrp));
 #pragma unroll
-        for (int th = 0; th < 1 + ph; ++th)
+        for (int r = 0; r < NBW; ++r) {
+          const int rr = wv * NBW + r;
+          const int mdl = rr / THI, mhl = rr - mdl * THI;
+          Vec4 b;
+          const int lvox = ((mdl + (t.off >> 2)) * LH + mhl + ((t.off >> 1) & 1)) * LW + col + (t.off & 1);
+          b.load(swz16(tile, lvox, kgrp));
 #pragma unroll
-          for (int tw = 0; tw < 1 + pw; ++tw) {
-            const int kd = pd ? (td ? 2 : 0) : 1, od_off = (pd && !td) ? 1 : 0;
-            const int kh = ph ? (th ? 2 : 0) : 1, oh_off = (ph && !th) ? 1 : 0;
-            const int kw = pw ? (tw ? 2 : 0) : 1, ow_off = (pw && !tw) ? 1 : 0;
-            const int tap = kd * 9 + kh * 3 + kw;
-            VecN<PL> a[MBB];
-            if (col < RM)
-              a[0].load(wts + (tap * RM + col) * 16 + 4 * (kgrp ^ ((col >> 1) & 3)));
-            else
-              a[0].zero();
-#pragma unroll
-            for (int r = 0; r < NBW; ++r) {
-              const int rr = wv * NBW + r;
-              const int mdl = rr / THI, mhl = rr - mdl * THI;
-              VecN<PL> b;
-              const int lvox = ((mdl + od_off) * LH + mhl + oh_off) * LW + col + ow_off;
-              const int qs = SWZ ? (kgrp ^ ((lvox >> 1) & 3)) : kgrp;
-              b.load(tile + lvox * VST + qs * PL);
-#pragma unroll
-              for (int j = 0; j < PL; ++j)
-#pragma unroll
-                for (int m = 0; m < MBB; ++m)
-                  acc[r][cls][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].v[j], b.v[j], acc[r][cls][m], 0, 0, 0);
-            }
-          }
+          for (int j = 0; j < PL; ++j)
+            acc[r][cls] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc[r][cls], 0, 0, 0);
+        }
+      }
     }
   }
   const size_t out_n = (size_t)n * g.Do * g.Ho * g.Wo;
-  if constexpr (COUT == 8) {
-    // 8-channel output (conv11, full resolution): the 32 output voxels of one (od, oh) row
-    // segment are exchanged through LDS so the skip read and the output store are single
-    // contiguous 1 KiB accesses (each 4-lane quad on 64 consecutive bytes) instead of 16-byte
-    // pieces at a 64-byte stride.
-    __shared__ __attribute__((aligned(16))) float ep[4][32 * 8];
-    float* eb = ep[wv];
-    const int co = kgrp * 4;
-    float4 al = make_float4(0.f, 0.f, 0.f, 0.f), sh = al;
-    if (kgrp < 2) {
-      al = *reinterpret_cast<const float4*>(alpha + co);
-      sh = *reinterpret_cast<const float4*>(shift + co);
-    }
-    const int ow = 2 * mw0 + (lane >> 1);  // voxel this lane stores (half lane & 1)
-#pragma unroll
-    for (int r = 0; r < NBW; ++r) {
-      const int rr = wv * NBW + r;
-      const int md = md0 + rr / THI, mh = mh0 + rr % THI;
-#pragma unroll
-      for (int pdh = 0; pdh < 4; ++pdh) {
-        if (kgrp < 2) {
-#pragma unroll
-          for (int pw = 0; pw < 2; ++pw) {
-            const floatx4 a = acc[r][pdh * 2 + pw][0];
-            *reinterpret_cast<float4*>(eb + (2 * col + pw) * 8 + co) =
-                make_float4(act(fmaf(a[0], al.x, sh.x), g.lo), act(fmaf(a[1], al.y, sh.y), g.lo),
-                            act(fmaf(a[2], al.z, sh.z), g.lo), act(fmaf(a[3], al.w, sh.w), g.lo));
-          }
-        }
-        __builtin_amdgcn_wave_barrier();
-        const float4 v = *reinterpret_cast<const float4*>(eb + lane * 4);
-        __builtin_amdgcn_wave_barrier();
-        const int od = 2 * md + (pdh >> 1), oh = 2 * mh + (pdh & 1);
-        if (md < g.Di && mh < g.Hi && ow < 2 * g.Wi) {
-          const size_t o = (out_n + ((size_t)od * g.Ho + oh) * g.Wo + ow) * 8 + (lane & 1) * 4;
-          const float4 s = skip ? *reinterpret_cast<const float4*>(skip + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-          *reinterpret_cast<float4*>(y + o) = make_float4(s.x + v.x, s.y + v.y, s.z + v.z, s.w + v.w);
-        }
-      }
-    }
-    return;
-  }
   const int mw = mw0 + col;
   if (mw >= g.Wi) return;
+  const int co = mg * 16 + kgrp * 4;
+  const float4 al = *reinterpret_cast<const float4*>(alpha + co);
+  const float4 sh = *reinterpret_cast<const float4*>(shift + co);
 #pragma unroll
-  for (int m = 0; m < MBB; ++m) {
-    const int co = (mg * MBB + m) * 16 + kgrp * 4;
-    if (co >= COUT) continue;
-    const float4 al = *reinterpret_cast<const float4*>(alpha + co);
-    const float4 sh = *reinterpret_cast<const float4*>(shift + co);
+  for (int r = 0; r < NBW; ++r) {
+    const int rr = wv * NBW + r;
+    const int md = md0 + rr / THI, mh = mh0 + rr % THI;
+    if (md >= g.Di || mh >= g.Hi) continue;
 #pragma unroll
-    for (int r = 0; r < NBW; ++r) {
-      const int rr = wv * NBW + r;
-      const int md = md0 + rr / THI, mh = mh0 + rr % THI;
-      if (md >= g.Di || mh >= g.Hi) continue;
-#pragma unroll
-      for (int cls = 0; cls < 8; ++cls) {
-        const int od = 2 * md + (cls >> 2), oh = 2 * mh + ((cls >> 1) & 1), ow = 2 * mw + (cls & 1);
-        const size_t o = (out_n + ((size_t)od * g.Ho + oh) * g.Wo + ow) * COUT + co;
-        const float4 s = skip ? *reinterpret_cast<const float4*>(skip + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 v;
-        v.x = s.x + act(fmaf(acc[r][cls][m][0], al.x, sh.x), g.lo);
-        v.y = s.y + act(fmaf(acc[r][cls][m][1], al.y, sh.y), g.lo);
-        v.z = s.z + act(fmaf(acc[r][cls][m][2], al.z, sh.z), g.lo);
-        v.w = s.w + act(fmaf(acc[r][cls][m][3], al.w, sh.w), g.lo);
-        *reinterpret_cast<float4*>(y + o) = v;
-      }
+    for (int cls = 0; cls < 8; ++cls) {
+      const int od = 2 * md + (cls >> 2), oh = 2 * mh + ((cls >> 1) & 1), ow = 2 * mw + (cls & 1);
+      const size_t o = (out_n + ((size_t)od * g.Ho + oh) * g.Wo + ow) * COUT + co;
+      const float4 s = skip ? *reinterpret_cast<const float4*>(skip + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(y + o) = add4(s, bn_act4(acc[r][cls], al, sh, g.lo));
     }
   }
 }
@@ -836,31 +823,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
                                                          int ntiles) {
   constexpr int C = 16, PL = 4, NWV = 4, NBW = TD * TH / NWV, NTH = NWV * 64;  // 4 waves per workgroup
   static_assert(TD * TH % NWV == 0, "rows split evenly over the waves");
-  constexpr int LW = 18, LH = TH + 2, LD = TD + 2, VST = 16;
+  constexpr int LW = 18, LH = TH + 2, LD = TD + 2;
   constexpr int NVOX = LD * LH * LW;
   constexpr int NLD = (NVOX * 4 + NTH - 1) / NTH;
-  __shared__ __attribute__((aligned(16))) float tile[NVOX * VST];
+  __shared__ __attribute__((aligned(16))) float tile[NVOX * 16];
   __shared__ __attribute__((aligned(16))) float wts[27 * 16 * 16];
   const int nws = (g.Wo + 15) / 16, nhs = (g.Ho + TH - 1) / TH, nds = (g.Do + TD - 1) / TD;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int col = lane & 15, kgrp = lane >> 4;
-  const int nxcd = gridDim.x >= 8 ? 8 : 1, per_xcd = gridDim.x / nxcd;
-  const int xcd = blockIdx.x % nxcd, kx = blockIdx.x / nxcd;
-  const int t_lo = (int)((long)ntiles * xcd / nxcd), t_hi = (int)((long)ntiles * (xcd + 1) / nxcd);
-  if (kx >= per_xcd) return;
-  struct TileCoord {
-    int n, od0, oh0, ow0;
-  };
-  auto coord = [&](int t) {
-    TileCoord c;
-    c.ow0 = (t % nws) * 16;
-    t /= nws;
-    c.oh0 = (t % nhs) * TH;
-    t /= nhs;
-    c.od0 = (t % nds) * TD;
-    c.n = t / nds;
-    return c;
-  };
+  const TileRange tr(ntiles);
+  if (tr.idle()) return;
+  auto coord = [&](int t) { return tile_coord(t, nws, nhs, nds, TH, TD); };
   float4 pf[NLD];
   auto fetch = [&](int t) {
     const TileCoord c = coord(t);
@@ -870,7 +843,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
       const int idx = threadIdx.x + NTH * k;
       const int vox = idx >> 2, q = idx & 3;
       const int lw = vox % LW, rest = vox / LW, lh = rest % LH, ld = rest / LH;
-      const int iw = c.ow0 - 1 + lw, ih = c.oh0 - 1 + lh, id = c.od0 - 1 + ld;
+      const int iw = c.w0 - 1 + lw, ih = c.h0 - 1 + lh, id = c.d0 - 1 + ld;
       pf[k] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (vox < NVOX && (unsigned)iw < (unsigned)g.Wi && (unsigned)ih < (unsigned)g.Hi && (unsigned)id < (unsigned)g.Di)
         pf[k] = *reinterpret_cast<const float4*>(x + (in_n + ((size_t)id * g.Hi + ih) * g.Wi + iw) * C + 4 * q);
@@ -881,41 +854,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     for (int k = 0; k < NLD; ++k) {
       const int idx = threadIdx.x + NTH * k;
       const int vox = idx >> 2, q = idx & 3;
-      if (vox < NVOX) *reinterpret_cast<float4*>(tile + vox * VST + 4 * (q ^ ((vox >> 1) & 3))) = pf[k];
+      if (vox < NVOX) *reinterpret_cast<float4*>(swz16(tile, vox, q)) = pf[k];
     }
   };
-  for (int idx = threadIdx.x; idx < 27 * 16 * 4; idx += NTH) {
-    const int q = idx & 3, row = (idx >> 2) & 15, tap = idx >> 6;
-    const float4 v = *reinterpret_cast<const float4*>(wpk + ((size_t)tap * C + row) * C + 4 * q);
-    *reinterpret_cast<float4*>(wts + (tap * 16 + row) * 16 + 4 * (q ^ ((row >> 1) & 3))) = v;
-  }
+  stage_weights16<C, C>(wts, wpk, 0, 0);
   const float4 al = *reinterpret_cast<const float4*>(alpha + kgrp * 4);
   const float4 sh = *reinterpret_cast<const float4*>(shift + kgrp * 4);
-  int t = t_lo + kx;
-  if (t < t_hi) {
+  int t = tr.first();
+  if (t < tr.end) {
     fetch(t);
     commit();
   }
   __syncthreads();
-  for (; t < t_hi; t += per_xcd) {
+  for (; t < tr.end; t += tr.step) {
     const TileCoord c = coord(t);
-    const int tn = t + per_xcd;
-    if (tn < t_hi) fetch(tn);
+    const int tn = t + tr.step;
+    if (tn < tr.end) fetch(tn);
     floatx4 acc[NBW];
 #pragma unroll
     for (int r = 0; r < NBW; ++r) acc[r] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int tap = 0; tap < 27; ++tap) {
       const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
-      VecN<PL> a;
-      a.load(wts + (tap * 16 + col) * 16 + 4 * (kgrp ^ ((col >> 1) & 3)));
-      VecN<PL> b[NBW];
+      Vec4 a;
+      a.load(swz16(wts + tap * 256, col, kgrp));
+      Vec4 b[NBW];
 #pragma unroll
       for (int r = 0; r < NBW; ++r) {
         const int rr = wv * NBW + r;
         const int odl = rr / TH, ohl = rr - odl * TH;
         const int lvox = ((odl + kd) * LH + ohl + kh) * LW + col + kw;
-        b[r].load(tile + lvox * VST + 4 * (kgrp ^ ((lvox >> 1) & 3)));
+        b[r].load(swz16(tile, lvox, kgrp));
       }
 #pragma unroll
       for (int j = 0; j < PL; ++j)
@@ -924,22 +893,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
           acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b[r].v[j], acc[r], 0, 0, 0);
       if (tap % (NBW > 2 ? 3 : 9) == (NBW > 2 ? 2 : 8)) __builtin_amdgcn_sched_barrier(0);  // bound the fragments in flight
     }
-    const int ow = c.ow0 + col;
+    const int ow = c.w0 + col;
     const size_t out_n = (size_t)c.n * g.Do * g.Ho * g.Wo;
 #pragma unroll
     for (int r = 0; r < NBW; ++r) {
       const int rr = wv * NBW + r;
-      const int od = c.od0 + rr / TH, oh = c.oh0 + rr % TH;
+      const int od = c.d0 + rr / TH, oh = c.h0 + rr % TH;
       if (ow >= g.Wo || od >= g.Do || oh >= g.Ho) continue;
-      float4 o;
-      o.x = act(fmaf(acc[r][0], al.x, sh.x), g.lo);
-      o.y = act(fmaf(acc[r][1], al.y, sh.y), g.lo);
-      o.z = act(fmaf(acc[r][2], al.z, sh.z), g.lo);
-      o.w = act(fmaf(acc[r][3], al.w, sh.w), g.lo);
-      *reinterpret_cast<float4*>(y + (out_n + ((size_t)od * g.Ho + oh) * g.Wo + ow) * C + kgrp * 4) = o;
+      *reinterpret_cast<float4*>(y + (out_n + ((size_t)od * g.Ho + oh) * g.Wo + ow) * C + kgrp * 4) =
+          bn_act4(acc[r], al, sh, g.lo);
     }
     __syncthreads();  // every wave is done with the tile
-    if (tn < t_hi) commit();
+    if (tn < tr.end) commit();
     __syncthreads();
   }
 }
@@ -965,14 +930,25 @@ static int persistent_grid(K kernel, long ntiles) {
   return (int)std::min<long>(ntiles, cap);
 }
 
+// tiles of TD x TH x 16 voxels over B volumes of d x h x w (the output grid of a conv, the input grid of a deconv)
+static long tile_count(int B, int d, int h, int w, int TD, int TH) {
+  return (long)B * ((d + TD - 1) / TD) * ((h + TH - 1) / TH) * ((w + 15) / 16);
+}
+
+// a persistent kernel (..., int ntiles) on min(ntiles, its residency) workgroups; max_wgs > 0 bounds the grid further
+template <typename K, typename... Args>
+static int launch_persistent(K kernel, long ntiles, int max_wgs, hipStream_t st, Args... args) {
+  long grid = persistent_grid(kernel, ntiles);
+  if (max_wgs > 0) grid = std::min<long>(grid, max_wgs);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, st, args..., (int)ntiles);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
 template <int TD, int TH>
 static int launch_conv_c16(const float* x, const float* w, const float* al, const float* sh, float* y, int B,
                            const Geo& g, hipStream_t st) {
-  const long ntiles = (long)B * ((g.Do + TD - 1) / TD) * ((g.Ho + TH - 1) / TH) * ((g.Wo + 15) / 16);
-  const int grid = persistent_grid(conv3d_c16_kernel<TD, TH>, ntiles);
-  hipLaunchKernelGGL((conv3d_c16_kernel<TD, TH>), dim3(grid), dim3(256), 0, st, x, w, al, sh, y, g, (int)ntiles);
-  TMVS_CHECK_LAUNCH();
-  return TMVS_OK;
+  return launch_persistent(conv3d_c16_kernel<TD, TH>, tile_count(B, g.Do, g.Ho, g.Wo, TD, TH), 0, st, x, w, al, sh, y, g);
 }
 
 // ---------------------------------------------------------------- conv1: 8 -> 16, stride 2, persistent
@@ -1004,23 +980,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void c
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int col = lane & 15, kgrp = lane >> 4;
   const int half = kgrp & 1, side = kgrp >> 1;
-  const int nxcd = gridDim.x >= 8 ? 8 : 1, per_xcd = gridDim.x / nxcd;
-  const int xcd = blockIdx.x % nxcd, kx = blockIdx.x / nxcd;
-  const int t_lo = (int)((long)ntiles * xcd / nxcd), t_hi = (int)((long)ntiles * (xcd + 1) / nxcd);
-  if (kx >= per_xcd) return;
-  struct TileCoord {
-    int n, od0, oh0, ow0;
-  };
-  auto coord = [&](int t) {
-    TileCoord c;
-    c.ow0 = (t % nws) * 16;
-    t /= nws;
-    c.oh0 = (t % nhs) * TH;
-    t /= nhs;
-    c.od0 = (t % nds) * TD;
-    c.n = t / nds;
-    return c;
-  };
+  const TileRange tr(ntiles);
+  if (tr.idle()) return;
+  auto coord = [&](int t) { return tile_coord(t, nws, nhs, nds, TH, TD); };
   float4 pf[NLD];
   auto fetch = [&](int t) {
     const TileCoord c = coord(t);
@@ -1030,7 +992,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void c
       const int idx = threadIdx.x + NTH * k;
       const int q = idx & 1, v = idx >> 1;
       const int lw = v % LW, row = v / LW, lh = row % LH, ld = row / LH;
-      const int iw = 2 * c.ow0 - 1 + lw, ih = 2 * c.oh0 - 1 + lh, id = 2 * c.od0 - 1 + ld;
+      const int iw = 2 * c.w0 - 1 + lw, ih = 2 * c.h0 - 1 + lh, id = 2 * c.d0 - 1 + ld;
       pf[k] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (idx < NQ && (unsigned)iw < (unsigned)g.Wi && (unsigned)ih < (unsigned)g.Hi && (unsigned)id < (unsigned)g.Di)
         pf[k] = *reinterpret_cast<const float4*>(x + (in_n + ((size_t)id * g.Hi + ih) * g.Wi + iw) * CIN + 4 * q);
@@ -1054,16 +1016,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void c
   const int co = kgrp * 4;
   const float4 al = *reinterpret_cast<const float4*>(alpha + co);
   const float4 sh = *reinterpret_cast<const float4*>(shift + co);
-  int t = t_lo + kx;
-  if (t < t_hi) {
+  int t = tr.first();
+  if (t < tr.end) {
     fetch(t);
     commit();
   }
   __syncthreads();
-  for (; t < t_hi; t += per_xcd) {
+  for (; t < tr.end; t += tr.step) {
     const TileCoord c = coord(t);
-    const int tn = t + per_xcd;
-    if (tn < t_hi) fetch(tn);
+    const int tn = t + tr.step;
+    if (tn < tr.end) fetch(tn);
     floatx4 acc[NBW];
 #pragma unroll
     for (int r = 0; r < NBW; ++r) acc[r] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -1091,22 +1053,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void c
 #pragma unroll
       for (int r = 0; r < NBW; ++r) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[r].w, acc[r], 0, 0, 0);
     }
-    const int ow = c.ow0 + col;
+    const int ow = c.w0 + col;
     const size_t out_n = (size_t)c.n * g.Do * g.Ho * g.Wo;
 #pragma unroll
     for (int r = 0; r < NBW; ++r) {
       const int rr = wv * NBW + r;
-      const int od = c.od0 + rr / TH, oh = c.oh0 + rr % TH;
+      const int od = c.d0 + rr / TH, oh = c.h0 + rr % TH;
       if (ow >= g.Wo || od >= g.Do || oh >= g.Ho) continue;
-      float4 o;
-      o.x = act(fmaf(acc[r][0], al.x, sh.x), g.lo);
-      o.y = act(fmaf(acc[r][1], al.y, sh.y), g.lo);
-      o.z = act(fmaf(acc[r][2], al.z, sh.z), g.lo);
-      o.w = act(fmaf(acc[r][3], al.w, sh.w), g.lo);
-      *reinterpret_cast<float4*>(y + (out_n + ((size_t)od * g.Ho + oh) * g.Wo + ow) * COUT + co) = o;
+      *reinterpret_cast<float4*>(y + (out_n + ((size_t)od * g.Ho + oh) * g.Wo + ow) * COUT + co) =
+          bn_act4(acc[r], al, sh, g.lo);
     }
     __syncthreads();
-    if (tn < t_hi) commit();
+    if (tn < tr.end) commit();
     __syncthreads();
   }
 }
@@ -1114,11 +1072,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void c
 template <int TD, int TH>
 static int launch_conv_s2c8_tile(const float* x, const float* w, const float* al, const float* sh, float* y, int B,
                                  const Geo& g, hipStream_t st) {
-  const long ntiles = (long)B * ((g.Do + TD - 1) / TD) * ((g.Ho + TH - 1) / TH) * ((g.Wo + 15) / 16);
-  const int grid = persistent_grid(conv3d_s2c8_tile_kernel<TD, TH>, ntiles);
-  hipLaunchKernelGGL((conv3d_s2c8_tile_kernel<TD, TH>), dim3(grid), dim3(256), 0, st, x, w, al, sh, y, g, (int)ntiles);
-  TMVS_CHECK_LAUNCH();
-  return TMVS_OK;
+  return launch_persistent(conv3d_s2c8_tile_kernel<TD, TH>, tile_count(B, g.Do, g.Ho, g.Wo, TD, TH), 0, st, x, w, al, sh, y,
+                           g);
 }
 
 // ---------------------------------------------------------------- launchers
@@ -1132,8 +1087,7 @@ struct LdsTile {
 template <int CIN, int COUT, int S, typename T, bool KDSKIP = false, bool TAPOUT = false>
 static int launch_conv(const float* x, const float* w, const float* al, const float* sh, float* y, int B,
                        const Geo& g, hipStream_t st) {
-  constexpr int MG = ((COUT + 15) / 16) / T::MBB;
-  const long nblk = (long)B * ((g.Do + T::TD - 1) / T::TD) * ((g.Ho + T::TH - 1) / T::TH) * ((g.Wo + 15) / 16) * MG;
+  const long nblk = tile_count(B, g.Do, g.Ho, g.Wo, T::TD, T::TH) * (COUT / 16 / T::MBB);
   hipLaunchKernelGGL((conv3d_lds_kernel<CIN, COUT, S, T::TD, T::TH, T::MBB, T::WS, KDSKIP, TAPOUT>),
                      dim3((unsigned)nblk), dim3(256), 0, st, x, w, al, sh, y, g);
   TMVS_CHECK_LAUNCH();
@@ -1172,25 +1126,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const int nws = (g.Wi + 15) / 16, nhs = (g.Hi + THI - 1) / THI, nds = (g.Di + TDI - 1) / TDI;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int col = lane & 15, kgrp = lane >> 4;
-  // XCD-contiguous tile ranges: workgroup b runs on XCD b % 8 (round-robin dispatch)
-  const int nxcd = gridDim.x >= 8 ? 8 : 1, per_xcd = gridDim.x / nxcd;
-  const int xcd = blockIdx.x % nxcd, kx = blockIdx.x / nxcd;
-  const int t_lo = (int)((long)ntiles * xcd / nxcd), t_hi = (int)((long)ntiles * (xcd + 1) / nxcd);
-  if (kx >= per_xcd) return;  // grid not a multiple of 8: the remainder idles
+  const TileRange tr(ntiles);
+  if (tr.idle()) return;
 
-  struct TileCoord {
-    int n, md0, mh0, mw0;
-  };
-  auto coord = [&](int t) {
-    TileCoord c;
-    c.mw0 = (t % nws) * 16;
-    t /= nws;
-    c.mh0 = (t % nhs) * THI;
-    t /= nhs;
-    c.md0 = (t % nds) * TDI;
-    c.n = t / nds;
-    return c;
-  };
+  auto coord = [&](int t) { return tile_coord(t, nws, nhs, nds, THI, TDI); };  // input-grid coordinates
   float4 pf[NLD];
   auto fetch = [&](int t) {  // global -> registers
     const TileCoord c = coord(t);
@@ -1200,7 +1139,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       const int idx = threadIdx.x + 256 * k;
       const int vox = idx >> 2, q = idx & 3;
       const int lw = vox % LW, rest = vox / LW, lh = rest % LH, ld = rest / LH;
-      const int iw = c.mw0 + lw, ih = c.mh0 + lh, id = c.md0 + ld;
+      const int iw = c.w0 + lw, ih = c.h0 + lh, id = c.d0 + ld;
       pf[k] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (vox < NVOX && iw < g.Wi && ih < g.Hi && id < g.Di)
         pf[k] = *reinterpret_cast<const float4*>(x + (in_n + ((size_t)id * g.Hi + ih) * g.Wi + iw) * CIN + 4 * q);
@@ -1211,10 +1150,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int k = 0; k < NLD; ++k) {
       const int idx = threadIdx.x + 256 * k;
       const int vox = idx >> 2, q = idx & 3;
-      if (vox < NVOX) *reinterpret_cast<float4*>(buf + vox * VST + 4 * (q ^ ((vox >> 1) & 3))) = pf[k];
+      if (vox < NVOX) *reinterpret_cast<float4*>(swz16(buf, vox, q)) = pf[k];
     }
   };
 
+  // stage_weights16 for 8 rows, spelled out: through a helper the kernel compiled to another instruction
+  // stream and measured slower at stage 3 (profiles/costreg_scaffold_resources.md)
   for (int idx = threadIdx.x; idx < 27 * 8 * 4; idx += 256) {
     const int q = idx & 3, row = (idx >> 2) & 7, tap = idx >> 5;
     const float4 v = *reinterpret_cast<const float4*>(wpk + ((size_t)tap * COUT + row) * CIN + 4 * q);
@@ -1226,23 +1167,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const int cq = 4 * (kgrp & 1);
   const float4 al = *reinterpret_cast<const float4*>(alpha + cq);
   const float4 sh = *reinterpret_cast<const float4*>(shift + cq);
-  auto wfrag = [&](int tap, VecN<PL>& a) { a.load(wts + (tap * 8 + co) * 16 + 4 * (kgrp ^ ((co >> 1) & 3))); };
+  auto wfrag = [&](int tap, Vec4& a) { a.load(swz16(wts + tap * 128, co, kgrp)); };
 
-  int t = t_lo + kx;
-  if (t < t_hi) {
+  int t = tr.first();
+  if (t < tr.end) {
     fetch(t);
     commit(tile[0]);
   }
   __syncthreads();
-  for (int it = 0; t < t_hi; t += per_xcd, ++it) {
+  for (int it = 0; t < tr.end; t += tr.step, ++it) {
     const float* cur = tile[it & 1];
     const TileCoord c = coord(t);
-    const int tn = t + per_xcd;
-    if (tn < t_hi) fetch(tn);
+    const int tn = t + tr.step;
+    if (tn < tr.end) fetch(tn);
     // skip rows of this tile: lane (pair) j of a 1 KiB output row, as the epilogue stores it (storing each
     // lane's own MFMA outputs without the exchange measured 110.2 -> 112.6 us in the step, r16g)
     const size_t out_n = (size_t)c.n * g.Do * g.Ho * g.Wo;
-    const int ow = 2 * c.mw0 + (lane >> 1);
+    const int ow = 2 * c.w0 + (lane >> 1);
     const size_t plane = (size_t)g.Ho * g.Wo * 8, row = (size_t)g.Wo * 8;  // output strides (floats)
     float4 sk[NBW][4];
     size_t oo[NBW];
@@ -1250,7 +1191,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
     for (int r = 0; r < NBW; ++r) {
       const int rr = wv * NBW + r;
-      const int md = c.md0 + rr / THI, mh = c.mh0 + rr % THI;
+      const int md = c.d0 + rr / THI, mh = c.h0 + rr % THI;
       ok[r] = md < g.Di && mh < g.Hi && ow < 2 * g.Wi;
       oo[r] = (out_n + ((size_t)(2 * md) * g.Ho + 2 * mh) * g.Wo + ow) * 8 + (lane & 1) * 4;
 #pragma unroll
@@ -1270,10 +1211,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       for (int td = 0; td < 1 + pd; ++td)
 #pragma unroll
         for (int th = 0; th < 1 + ph; ++th) {
-          const int kd = pd ? (td ? 2 : 0) : 1, od_off = (pd && !td) ? 1 : 0;
-          const int kh = ph ? (th ? 2 : 0) : 1, oh_off = (ph && !th) ? 1 : 0;
-          const int tap_base = kd * 9 + kh * 3;
-          VecN<PL> a1, a2;
+          const ParityTap d = parity_tap(pd, td), h = parity_tap(ph, th);
+          const int tap_base = d.k * 9 + h.k * 3;
+          Vec4 a1, a2;
           wfrag(tap_base + (hi ? 2 : 1), a1);  // rows 0-7: kw=1, rows 8-15: kw=2 (input column m)
           if (hi)
             wfrag(tap_base + 0, a2);           // rows 8-15: kw=0 (input column m+1)
@@ -1283,10 +1223,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
           for (int r = 0; r < NBW; ++r) {
             const int rr = wv * NBW + r;
             const int mdl = rr / THI, mhl = rr - mdl * THI;
-            const int lv = ((mdl + od_off) * LH + mhl + oh_off) * LW + col;
-            VecN<PL> b1, b2;
-            b1.load(cur + lv * VST + 4 * (kgrp ^ ((lv >> 1) & 3)));
-            b2.load(cur + (lv + 1) * VST + 4 * (kgrp ^ (((lv + 1) >> 1) & 3)));
+            const int lv = ((mdl + d.off) * LH + mhl + h.off) * LW + col;
+            Vec4 b1, b2;
+            b1.load(swz16(cur, lv, kgrp));
+            b2.load(swz16(cur, lv + 1, kgrp));
 #pragma unroll
             for (int j = 0; j < PL; ++j)
               acc[r][pdh] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.v[j], b1.v[j], acc[r][pdh], 0, 0, 0);
@@ -1303,19 +1243,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int r = 0; r < NBW; ++r)
 #pragma unroll
       for (int pdh = 0; pdh < 4; ++pdh) {
-        const floatx4 a = acc[r][pdh];
-        *reinterpret_cast<float4*>(eb + (2 * col + (kgrp >> 1)) * 8 + cq) =
-            make_float4(act(fmaf(a[0], al.x, sh.x), g.lo), act(fmaf(a[1], al.y, sh.y), g.lo), act(fmaf(a[2], al.z, sh.z), g.lo),
-                        act(fmaf(a[3], al.w, sh.w), g.lo));
+        *reinterpret_cast<float4*>(eb + (2 * col + (kgrp >> 1)) * 8 + cq) = bn_act4(acc[r][pdh], al, sh, g.lo);
         __builtin_amdgcn_wave_barrier();
         const float4 v = *reinterpret_cast<const float4*>(eb + lane * 4);
         __builtin_amdgcn_wave_barrier();
-        const float4 sv = sk[r][pdh];
-        if (ok[r])
-          *reinterpret_cast<float4*>(y + oo[r] + (pdh >> 1) * plane + (pdh & 1) * row) =
-              make_float4(sv.x + v.x, sv.y + v.y, sv.z + v.z, sv.w + v.w);
+        if (ok[r]) *reinterpret_cast<float4*>(y + oo[r] + (pdh >> 1) * plane + (pdh & 1) * row) = add4(sk[r][pdh], v);
       }
-    if (tn < t_hi) commit(tile[(it + 1) & 1]);
+    if (tn < tr.end) commit(tile[(it + 1) & 1]);
     __syncthreads();
   }
 }
@@ -1323,12 +1257,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 template <int TDI, int THI>
 static int launch_deconv_c8(const float* x, const float* w, const float* al, const float* sh, const float* skip,
                             float* y, int B, const Geo& g, hipStream_t st) {
-  const long ntiles = (long)B * ((g.Di + TDI - 1) / TDI) * ((g.Hi + THI - 1) / THI) * ((g.Wi + 15) / 16);
-  const long grid = persistent_grid(deconv3d_c8_kernel<TDI, THI>, ntiles);
-  hipLaunchKernelGGL((deconv3d_c8_kernel<TDI, THI>), dim3((unsigned)grid), dim3(256), 0, st, x, w, al, sh, skip, y, g,
-                     (int)ntiles);
-  TMVS_CHECK_LAUNCH();
-  return TMVS_OK;
+  return launch_persistent(deconv3d_c8_kernel<TDI, THI>, tile_count(B, g.Di, g.Hi, g.Wi, TDI, THI), 0, st, x, w, al, sh, skip,
+                           y, g);
 }
 
 // ---------------------------------------------------------------- deconv 32 -> 16 (conv9), persistent
@@ -1348,23 +1278,12 @@ static int launch_deconv_c8(const float* x, const float* w, const float* al, con
 // tile's 8 skip voxels, then the next tile's staging loads) and each class's stores right behind its last
 // MFMA in the second. Stage 2 / 3 per call: 53.6 / 52.0 us generic, 48 us for the plain persistent form,
 // 38.5 / 37.7 us as scheduled here.
-struct DeconvTap {
-  int cls, tap, off;  // parity class, weight tap, input voxel offset (bit 2: depth, 1: row, 0: column)
-};
-// tap i (0 .. 12 / 13) of one stream, in deconv3d_lds_kernel's (class, td, th, tw) order
+// tap i (0 .. 12 / 13) of one stream, in deconv3d_lds_kernel's (class, tap of the class) order
 constexpr DeconvTap deconv_stream_tap(int stream, int i) {
-  int k = 0;
   for (int cls = 0; cls < 8; ++cls) {
     if ((cls == 0 || cls == 3 || cls == 7) != (stream == 0)) continue;
-    const int pd = cls >> 2, ph = (cls >> 1) & 1, pw = cls & 1;
-    for (int td = 0; td < 1 + pd; ++td)
-      for (int th = 0; th < 1 + ph; ++th)
-        for (int tw = 0; tw < 1 + pw; ++tw) {
-          const int kd = pd ? (td ? 2 : 0) : 1, od_off = (pd && !td) ? 1 : 0;
-          const int kh = ph ? (th ? 2 : 0) : 1, oh_off = (ph && !th) ? 1 : 0;
-          const int kw = pw ? (tw ? 2 : 0) : 1, ow_off = (pw && !tw) ? 1 : 0;
-          if (k++ == i) return DeconvTap{cls, kd * 9 + kh * 3 + kw, od_off * 4 + oh_off * 2 + ow_off};
-        }
+    if (i < deconv_class_taps(cls)) return deconv_class_tap(cls, i);
+    i -= deconv_class_taps(cls);
   }
   return DeconvTap{-1, 0, 0};
 }
@@ -1390,35 +1309,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const float* __restrict__ shift, const float* __restrict__ skip, float* __restrict__ y, Geo g, int ntiles) {
   constexpr int CIN = 32, COUT = 16, PL = 4, NCH = 2;
   static_assert(TDI * THI == 4, "one input-grid row per wave");
-  constexpr int LW = 17, LH = THI + 1, LD = TDI + 1, VST = 16;
+  constexpr int LW = 17, LH = THI + 1, LD = TDI + 1;
   constexpr int NVOX = LD * LH * LW;
   constexpr int NQ = NVOX * 2 * PL;          // float4 quads per tile: a voxel's 32 channels are 8
   constexpr int NLD = (NQ + 255) / 256;      // staging loads per thread and tile
-  __shared__ __attribute__((aligned(16))) float tile[NCH][NVOX * VST];
+  __shared__ __attribute__((aligned(16))) float tile[NCH][NVOX * 16];
   __shared__ __attribute__((aligned(16))) float wts[NCH][27 * 16 * 16];
 
   const int nws = (g.Wi + 15) / 16, nhs = (g.Hi + THI - 1) / THI, nds = (g.Di + TDI - 1) / TDI;
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int col = lane & 15, kgrp = lane >> 4;
-  // XCD-contiguous tile ranges: workgroup b runs on XCD b % 8 (round-robin dispatch)
-  const int nxcd = gridDim.x >= 8 ? 8 : 1, per_xcd = gridDim.x / nxcd;
-  const int xcd = blockIdx.x % nxcd, kx = blockIdx.x / nxcd;
-  const int t_lo = (int)((long)ntiles * xcd / nxcd), t_hi = (int)((long)ntiles * (xcd + 1) / nxcd);
-  if (kx >= per_xcd) return;  // grid not a multiple of 8: the remainder idles
-
-  struct TileCoord {
-    int n, md0, mh0, mw0;
-  };
-  auto coord = [&](int t) {
-    TileCoord c;
-    c.mw0 = (t % nws) * 16;
-    t /= nws;
-    c.mh0 = (t % nhs) * THI;
-    t /= nhs;
-    c.md0 = (t % nds) * TDI;
-    c.n = t / nds;
-    return c;
-  };
+  const TileRange tr(ntiles);
+  if (tr.idle()) return;
+  auto coord = [&](int t) { return tile_coord(t, nws, nhs, nds, THI, TDI); };  // input-grid coordinates
   const uint32_t in_bytes = (uint32_t)g.Di * g.Hi * g.Wi * CIN * 4;     // one sample (host: < 2 GB)
   const uint32_t out_bytes = (uint32_t)g.Do * g.Ho * g.Wo * COUT * 4;   // (host: < 2 GB)
   float4 pf[NLD];
@@ -1433,13 +1336,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto fetch_of = [&](int t, bool live) {
     const TileCoord c = coord(live ? t : 0);
     return Fetch{Buf(x + (size_t)c.n * g.Di * g.Hi * g.Wi * CIN, in_bytes), c,
-                 ((c.md0 * g.Hi + c.mh0) * g.Wi + c.mw0) * CIN * 4 /* the tile's first voxel */, live};
+                 ((c.d0 * g.Hi + c.h0) * g.Wi + c.w0) * CIN * 4 /* the tile's first voxel */, live};
   };
   auto fetch1 = [&](const Fetch& f, int k) {
     const int idx = threadIdx.x + 256 * k;
     const int vox = idx >> 3, q8 = idx & 7;
     const int lw = vox % LW, rest = vox / LW, lh = rest % LH, ld = rest / LH;
-    const bool ok = f.live && idx < NQ && f.c.mw0 + lw < g.Wi && f.c.mh0 + lh < g.Hi && f.c.md0 + ld < g.Di;
+    const bool ok = f.live && idx < NQ && f.c.w0 + lw < g.Wi && f.c.h0 + lh < g.Hi && f.c.d0 + ld < g.Di;
     pf[k] = f.xb.ld4(ok ? (((ld * g.Hi + lh) * g.Wi + lw) * CIN + 4 * q8) * 4 : Buf::kOOB, f.soff);
   };
   auto fetch = [&](int t, bool live) {
@@ -1453,7 +1356,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int idx = threadIdx.x + 256 * k;
       const int vox = idx >> 3, q8 = idx & 7;
       const int ch = q8 >> 2, q = q8 & 3;
-      if (idx < NQ) *reinterpret_cast<float4*>(tile[ch] + vox * VST + 4 * (q ^ ((vox >> 1) & 3))) = pf[k];
+      if (idx < NQ) *reinterpret_cast<float4*>(swz16(tile[ch], vox, q)) = pf[k];
     }
   };
 
@@ -1467,28 +1370,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int idx = threadIdx.x + 256 * k;  // quad idx of wpk: [tap][row][ch][q]
     wreg[k] = wb.ld4(idx < NWQ ? idx * 16 : Buf::kOOB);
   }
-  int t = t_lo + kx;
-  fetch(t, t < t_hi);
+  int t = tr.first();
+  fetch(t, t < tr.end);
 #pragma unroll
   for (int k = 0; k < NWL; ++k) {
     const int idx = threadIdx.x + 256 * k;
     const int q = idx & 3, ch = (idx >> 2) & 1, row = (idx >> 3) & 15, tap = idx >> 7;
-    if (idx < NWQ) *reinterpret_cast<float4*>(wts[ch] + (tap * 16 + row) * 16 + 4 * (q ^ ((row >> 1) & 3))) = wreg[k];
+    if (idx < NWQ) *reinterpret_cast<float4*>(swz16(wts[ch] + tap * 256, row, q)) = wreg[k];
   }
   const int co = kgrp * 4;
   const float4 al = *reinterpret_cast<const float4*>(alpha + co);
   const float4 sh = *reinterpret_cast<const float4*>(shift + co);
   const int mdl = wv / THI, mhl = wv - mdl * THI;  // the wave's input-grid row of the tile
-  const int woff = col * 16 + 4 * (kgrp ^ ((col >> 1) & 3));  // the lane's A fragment within a tap
+  const int woff = swz16(col, kgrp);  // the lane's A fragment within a tap
 
   commit();
   __syncthreads();
-  for (; t < t_hi; t += per_xcd) {
+  for (; t < tr.end; t += tr.step) {
     const TileCoord c = coord(t);
-    const int tn = t + per_xcd;
-    const bool more = tn < t_hi;
+    const int tn = t + tr.step;
+    const bool more = tn < tr.end;
     const Fetch fn = fetch_of(tn, more);
-    const int md = c.md0 + mdl, mh = c.mh0 + mhl, mw = c.mw0 + col;
+    const int md = c.d0 + mdl, mh = c.h0 + mhl, mw = c.w0 + col;
     const bool ok = md < g.Di && mh < g.Hi && mw < g.Wi;
     const size_t out_n = (size_t)c.n * g.Do * g.Ho * g.Wo * COUT;
     const Buf sb(skip ? skip + out_n : nullptr, skip ? out_bytes : 0u), yb(y + out_n, out_bytes);
@@ -1503,24 +1406,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     floatx4 acc[8];
 #pragma unroll
     for (int cls = 0; cls < 8; ++cls) acc[cls] = floatx4{0.f, 0.f, 0.f, 0.f};
-    // deconv3d_lds_kernel's COUT == 16 epilogue of one class (a lane outside the volume stores nothing)
+    // deconv3d_lds_kernel's epilogue of one class (a lane outside the volume stores nothing)
     auto epilogue = [&](auto cc) {
       constexpr int cls = decltype(cc)::value;
-      const float4 s = sk[cls];
-      float4 v;
-      v.x = s.x + act(fmaf(acc[cls][0], al.x, sh.x), g.lo);
-      v.y = s.y + act(fmaf(acc[cls][1], al.y, sh.y), g.lo);
-      v.z = s.z + act(fmaf(acc[cls][2], al.z, sh.z), g.lo);
-      v.w = s.w + act(fmaf(acc[cls][3], al.w, sh.w), g.lo);
-      yb.st4(v, so[cls]);
+      yb.st4(add4(sk[cls], bn_act4(acc[cls], al, sh, g.lo)), so[cls]);
     };
     // 28 steps (chunk, tap pair). The A fragments of step s + 1 are read from LDS before step s's MFMAs
     // (read right before their own MFMAs, every step opened with an exposed LDS round trip), and chunk 1's
     // B fragments one per step during chunk 0's first 8.
-    VecN<PL> b[NCH][8], a[2][2];
+    Vec4 b[NCH][8], a[2][2];
     auto bload = [&](int ch, int off) {
       const int lvox = ((mdl + (off >> 2)) * LH + mhl + ((off >> 1) & 1)) * LW + col + (off & 1);
-      b[ch][off].load(tile[ch] + lvox * VST + 4 * (kgrp ^ ((lvox >> 1) & 3)));
+      b[ch][off].load(swz16(tile[ch], lvox, kgrp));
     };
 #pragma unroll
     for (int off = 0; off < 8; ++off) bload(0, off);
@@ -1575,21 +1472,15 @@ constexpr int kC16pMinTilesNum = 3, kC16pMinTilesDen = 2;
 template <int TDI, int THI>
 static int launch_deconv_c16p(const float* x, const float* w, const float* al, const float* sh, const float* skip,
                               float* y, int B, const Geo& g, hipStream_t st, int max_wgs = 0) {
-  const long ntiles = (long)B * ((g.Di + TDI - 1) / TDI) * ((g.Hi + THI - 1) / THI) * ((g.Wi + 15) / 16);
-  long grid = persistent_grid(deconv3d_c16p_kernel<TDI, THI>, ntiles);
-  if (max_wgs > 0) grid = std::min<long>(grid, max_wgs);
-  hipLaunchKernelGGL((deconv3d_c16p_kernel<TDI, THI>), dim3((unsigned)grid), dim3(256), 0, st, x, w, al, sh, skip, y, g,
-                     (int)ntiles);
-  TMVS_CHECK_LAUNCH();
-  return TMVS_OK;
+  return launch_persistent(deconv3d_c16p_kernel<TDI, THI>, tile_count(B, g.Di, g.Hi, g.Wi, TDI, THI), max_wgs, st, x, w, al,
+                           sh, skip, y, g);
 }
 
-template <int CIN, int COUT, int TDI, int THI, int MBB>
+template <int CIN, int COUT, int TDI, int THI>
 static int launch_deconv(const float* x, const float* w, const float* al, const float* sh, const float* skip,
                          float* y, int B, const Geo& g, hipStream_t st) {
-  constexpr int MG = ((COUT + 15) / 16) / MBB;
-  const long nblk = (long)B * ((g.Di + TDI - 1) / TDI) * ((g.Hi + THI - 1) / THI) * ((g.Wi + 15) / 16) * MG;
-  hipLaunchKernelGGL((deconv3d_lds_kernel<CIN, COUT, TDI, THI, MBB>), dim3((unsigned)nblk), dim3(256), 0, st, x, w,
+  const long nblk = tile_count(B, g.Di, g.Hi, g.Wi, TDI, THI) * (COUT / 16);
+  hipLaunchKernelGGL((deconv3d_lds_kernel<CIN, COUT, TDI, THI>), dim3((unsigned)nblk), dim3(256), 0, st, x, w,
                      al, sh, skip, y, g);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
@@ -1597,20 +1488,7 @@ static int launch_deconv(const float* x, const float* w, const float* al, const 
 
 static int conv_dispatch(const float* x, int B, int cin, int d, int h, int w, const float* wpk, const float* al,
                          const float* sh, int cout, int stride, float* y, hipStream_t st, float lo = 0.f) {
-  Geo g;
-  g.lo = lo;
-  g.Di = d;
-  g.Hi = h;
-  g.Wi = w;
-  if (stride == 1) {
-    g.Do = d;
-    g.Ho = h;
-    g.Wo = w;
-  } else {
-    g.Do = (d - 1) / 2 + 1;
-    g.Ho = (h - 1) / 2 + 1;
-    g.Wo = (w - 1) / 2 + 1;
-  }
+  const Geo g = Geo::conv(d, h, w, stride, lo);
   // the MFMA kernels address one sample's input through a buffer with 32-bit byte offsets
   if ((long long)d * h * w * cin * 4 >= (1LL << 31)) return TMVS_ERR_SHAPE;
   // output depth <= 2 (the coarse levels of a D = 8 stage): every wave has a kd slice that lies wholly in
@@ -1649,22 +1527,15 @@ enum class Route { kAuto, kGeneric, kPersistent };
 static int deconv_dispatch(const float* x, int B, int cin, int d, int h, int w, const float* wpk, const float* al,
                            const float* sh, int cout, const float* skip, float* y, hipStream_t st, float lo = 0.f,
                            Route route = Route::kAuto, int max_wgs = 0) {
-  Geo g;
-  g.lo = lo;
-  g.Di = d;
-  g.Hi = h;
-  g.Wi = w;
-  g.Do = 2 * d;
-  g.Ho = 2 * h;
-  g.Wo = 2 * w;
+  const Geo g = Geo::deconv(d, h, w, lo);
   // (TDI, THI) input tile: 2 x 2 for an even input depth, 1 x 4 for an odd one
   const bool even = g.Di % 2 == 0;
   int (*launch)(const float*, const float*, const float*, const float*, const float*, float*, int, const Geo&,
                 hipStream_t) = nullptr;
   if (cin == 64 && cout == 32)
-    launch = even ? launch_deconv<64, 32, 2, 2, 1> : launch_deconv<64, 32, 1, 4, 1>;
+    launch = even ? launch_deconv<64, 32, 2, 2> : launch_deconv<64, 32, 1, 4>;
   else if (cin == 32 && cout == 16)
-    launch = even ? launch_deconv<32, 16, 2, 2, 1> : launch_deconv<32, 16, 1, 4, 1>;
+    launch = even ? launch_deconv<32, 16, 2, 2> : launch_deconv<32, 16, 1, 4>;
   else if (cin == 16 && cout == 8)  // W-parity outputs packed into the 16 MFMA rows
     launch = even ? launch_deconv_c8<2, 2> : launch_deconv_c8<1, 4>;
   if (cin == 32 && cout == 16 && route != Route::kGeneric) {
@@ -1672,7 +1543,7 @@ static int deconv_dispatch(const float* x, int B, int cin, int d, int h, int w, 
     // offsets, and is taken from kC16pMinTilesNum / kC16pMinTilesDen tiles per resident workgroup on
     const bool fits = (long long)g.Do * g.Ho * g.Wo * cout * 4 < (1LL << 31);  // (the input is a quarter of it)
     const int tdi = even ? 2 : 1, thi = even ? 2 : 4;
-    const long ntiles = (long)B * ((d + tdi - 1) / tdi) * ((h + thi - 1) / thi) * ((w + 15) / 16);
+    const long ntiles = tile_count(B, d, h, w, tdi, thi);
     const int cap = even ? persistent_cap(deconv3d_c16p_kernel<2, 2>) : persistent_cap(deconv3d_c16p_kernel<1, 4>);
     if (route == Route::kPersistent && !fits) return TMVS_ERR_SHAPE;
     if (route == Route::kPersistent || (fits && ntiles * kC16pMinTilesDen >= (long)cap * kC16pMinTilesNum))
@@ -1724,6 +1595,14 @@ extern "C" int tmvs_deconv3d_bn_relu_add_persistent(const float* x, int batch, i
                          Route::kPersistent, max_workgroups);
 }
 
+static int launch_conv0(const float* x, float* y, int batch, int D, int H, int W, const float* wt, const float* al,
+                        const float* sh, float lo, hipStream_t st) {
+  const dim3 grid((unsigned)(((W + kProbCols - 1) / kProbCols) * ((H + 3) / 4) * batch * ((D + kDChunk - 1) / kDChunk)));
+  hipLaunchKernelGGL(conv0_kernel, grid, dim3(256), 0, st, x, y, D, H, W, wt, al, sh, lo);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
 // prob (8 -> 1) raw logits: one row per wave (two measured 42.3 -> 44.9 us at stage 1's D = 48, r16c)
 static int launch_prob(const float* x, float* y, int batch, int D, int H, int W, const float* wt, hipStream_t st) {
   constexpr int NR = 1;
@@ -1762,10 +1641,7 @@ extern "C" int tmvs_conv3d_mfma(const float* x, int batch, int cin, int d, int h
   hipStream_t st = (hipStream_t)stream;
   if (!transposed && stride == 1 && cin == 1 && cout == 8) {  // conv0's VALU kernel, raw epilogue
     if ((long long)d * h * w * 32 >= (1LL << 31)) return TMVS_ERR_SHAPE;
-    const dim3 grid((unsigned)(((w + kProbCols - 1) / kProbCols) * ((h + 3) / 4) * batch * ((d + kDChunk - 1) / kDChunk)));
-    hipLaunchKernelGGL(conv0_kernel, grid, dim3(256), 0, st, x, y, d, h, w, wpk, al, sh, lo);
-    TMVS_CHECK_LAUNCH();
-    return TMVS_OK;
+    return launch_conv0(x, y, batch, d, h, w, wpk, al, sh, lo, st);
   }
   if (!transposed && stride == 1 && cin == 8 && cout == 1) {  // prob's VALU kernel (prob packing)
     if ((long long)d * h * w * 32 >= (1LL << 31)) return TMVS_ERR_SHAPE;
@@ -1832,10 +1708,7 @@ static int costregnet_trunk(const float* x, int batch, int depth, int height, in
   const int D2 = D1 / 2, H2 = H1 / 2, W2 = W1 / 2;
   const int D3 = D2 / 2, H3 = H2 / 2, W3 = W2 / 2;
   int rc;
-  const dim3 g0x((unsigned)(((W0 + kProbCols - 1) / kProbCols) * ((H0 + 3) / 4) * batch * ((D0 + kDChunk - 1) / kDChunk)));
-  hipLaunchKernelGGL(conv0_kernel, g0x, dim3(256), 0, st, x, c0, D0, H0, W0, w->w[0], w->alpha[0], w->shift[0],
-                     0.f);
-  TMVS_CHECK_LAUNCH();
+  if ((rc = launch_conv0(x, c0, batch, D0, H0, W0, w->w[0], w->alpha[0], w->shift[0], 0.f, st))) return rc;
   if ((rc = conv_dispatch(c0, batch, c, D0, H0, W0, w->w[1], w->alpha[1], w->shift[1], 2 * c, 2, c1, st))) return rc;
   if ((rc = conv_dispatch(c1, batch, 2 * c, D1, H1, W1, w->w[2], w->alpha[2], w->shift[2], 2 * c, 1, c2, st)))
     return rc;
