@@ -329,7 +329,11 @@ int tmvs_warp_corr_backward(const float* ref_fea, const float* src_fea, const fl
  *   tmvs_aggregate_train: sim [D][H][W] = sum_v sims_v w_v / (1e-5 + sum_v w_v) (views in order),
  *     wsum [H][W]; view_w read at (y >> vw_shift, x >> vw_shift) of [V][H>>s][W>>s].
  *   tmvs_aggregate_train_backward: dsims = dsim / wsum * w_v, and (dview_w non-NULL)
- *     dview_w = sum_d dsim / wsum * (sims_v - sim).
+ *     dview_w [V][H][W] = sum_d dsim / wsum * (sims_v - sim), the difference formed in fp64 from sims
+ *     and view_w (sim must be non-NULL but is not read: its rounding would swallow the difference).
+ *   Both aggregate entry points: vw_shift in [0, 4], height and width multiples of 2^vw_shift
+ *     (nearest up-sampling always produces such sizes; a remainder would index the next row's, the
+ *     next view's or no weight), else TMVS_ERR_SHAPE before any launch.
  *   tmvs_pixelwise_train_backward: adds the PixelwiseNet path to dsims and its parameter gradients
  *     to dpwp [201] (accumulated: zero it first).
  * All reductions: fp64 block partials + fixed-order combines (deterministic).                  */

@@ -326,6 +326,106 @@ def test_training_primitive_validation_without_gpu(lib):
     assert dm(p, p, p, 16, 2.5, p, lib.tmvs_depth_metrics_workspace(16) - 1, q, None) == ARG
 
 
+def test_view_aggregation_validation_without_gpu(lib):
+    """tmvs_aggregate_train and tmvs_aggregate_train_backward read the view weights at (y >> vw_shift,
+    x >> vw_shift) of an [H >> vw_shift][W >> vw_shift] map per view. A height or width with any of its low
+    vw_shift bits set would read the next row's weight in the last column and the next view's map (past the
+    buffer, for the last view) in the last row: TMVS_ERR_SHAPE, as is a shift above 4 (the model uses 0, 1, 2).
+    Null pointers, non-positive sizes and a negative shift stay TMVS_ERR_ARG. All before any launch (the
+    pointers are host memory that is never read), and every call has exactly one thing wrong with it."""
+    ARG, SHAPE = -1, -2
+    backing = np.zeros(256, np.float32)
+    p = (backing.ctypes.data + 63) & ~63
+    fwd, bwd = lib.tmvs_aggregate_train, lib.tmvs_aggregate_train_backward
+
+    def both(v, d, h, w, shift):
+        return (fwd(p, p, v, d, h, w, shift, p, p, None), bwd(p, p, p, p, p, v, d, h, w, shift, p, p, None),
+                bwd(p, p, p, p, p, v, d, h, w, shift, p, None, None))
+
+    for h, w, shift in ((9, 28, 1), (8, 29, 1), (9, 29, 1), (1, 8, 1), (8, 1, 1), (10, 28, 2), (12, 30, 2), (9, 12, 2),
+                        (12, 13, 2), (4, 12, 3), (8, 4, 3), (16, 24, 4), (8, 16, 4), (1, 1, 1), (3, 3, 2)):
+        for v, d in ((1, 1), (3, 8), (5, 48)):
+            assert both(v, d, h, w, shift) == (SHAPE,) * 3, (v, d, h, w, shift)
+    for shift in (5, 6, 15, 30, 31, 32, 33, 64, 1 << 20, (1 << 31) - 1):  # whatever the size, also one it divides
+        assert both(2, 4, 1 << 12, 1 << 12, shift) == (SHAPE,) * 3, shift
+        assert both(2, 4, 16, 16, shift) == (SHAPE,) * 3, shift
+    for shift in (-1, -2, -(1 << 31)):
+        assert both(2, 4, 16, 16, shift) == (ARG,) * 3, shift
+    for dims in ((0, 4, 8, 8), (2, 0, 8, 8), (2, 4, 0, 8), (2, 4, 8, 0), (-1, 4, 8, 8), (2, -4, 8, 8), (2, 4, -8, 8),
+                 (2, 4, 8, -8)):
+        for shift in (0, 1, 2):
+            assert both(*dims, shift) == (ARG,) * 3, (dims, shift)
+    for shift in (0, 1, 2, 3, 4):
+        for nul in range(4):
+            a = [p, p, p, p]
+            a[nul] = None
+            assert fwd(a[0], a[1], 2, 4, 16, 32, shift, a[2], a[3], None) == ARG, (nul, shift)
+        for nul in range(6):  # dview_w is optional: NULL there is no error
+            a = [p, p, p, p, p, p]
+            a[nul] = None
+            assert bwd(a[0], a[1], a[2], a[3], a[4], 2, 4, 16, 32, shift, a[5], p, None) == ARG, (nul, shift)
+
+    # ---- the PixelwiseNet entry points next to them (csrc/pw_train.hip): nulls, sizes and the workspace
+    pf, pb = lib.tmvs_pixelwise_train_forward, lib.tmvs_pixelwise_train_backward
+    big = 1 << 40
+    need = lib.tmvs_pixelwise_train_workspace()
+    assert need >= (1024 * 160 + 2 + 16 + 25 + 160 + 16) * 8
+    for nul in range(6):
+        a = [p, p, p, p, p, p]
+        a[nul] = None
+        assert pf(a[0], 2, 4, 8, 8, a[1], a[2], big, a[3], a[4], a[5], None) == ARG, nul
+    for nul in range(9):
+        a = [p] * 9
+        a[nul] = None
+        assert pb(a[0], 2, 4, 8, 8, a[1], a[2], a[3], a[4], a[5], a[6], big, a[7], a[8], None) == ARG, nul
+    for dims in ((0, 4, 8, 8), (2, 0, 8, 8), (2, 4, 0, 8), (2, 4, 8, 0), (-1, 4, 8, 8), (2, 4, 8, -8)):
+        assert pf(p, *dims, p, p, big, p, p, p, None) == ARG, dims
+        assert pb(p, *dims, p, p, p, p, p, p, big, p, p, None) == ARG, dims
+    assert pf(p, 2, 4, 8, 8, p, p, need - 1, p, p, p, None) == ARG
+    assert pb(p, 2, 4, 8, 8, p, p, p, p, p, p, need - 1, p, p, None) == ARG
+
+
+def test_loss_and_adam_validation_without_gpu(lib):
+    """tmvs_entropy_loss and the two Adam steps (csrc/loss.hip, csrc/optim.hip): what they refuse before any
+    launch, and the loss workspace formula either side of a 256-pixel block."""
+    ARG, SHAPE = -1, -2
+    backing = np.zeros(256, np.float32)
+    p = (backing.ctypes.data + 63) & ~63
+    big = 1 << 40
+    el = lib.tmvs_entropy_loss
+    for nul in range(6):  # prob, depth_values, depth_gt, mask, workspace, out; the three maps after out are optional
+        a = [p] * 6
+        a[nul] = None
+        for per_pixel in (0, 1):
+            assert el(a[0], a[1], per_pixel, a[2], a[3], 1, 4, 8, 8, 1.0, a[4], big, a[5], None, None, None,
+                      None) == ARG, nul
+    for dims in ((0, 4, 8, 8), (1, 0, 8, 8), (1, 4, 0, 8), (1, 4, 8, 0), (-1, 4, 8, 8), (1, 4, 8, -8)):
+        assert el(p, p, 0, p, p, *dims, 1.0, p, big, p, p, p, p, None) == SHAPE, dims
+    assert el(p, p, 0, p, p, 1, 4, 1 << 12, 1 << 11, 1.0, p, big, p, p, p, p, None) == SHAPE  # HW * 256 >= 2^31
+    assert el(p, p, 0, p, p, 2, 4, 3, 171, 1.0, p, lib.tmvs_entropy_loss_workspace(2, 3, 171) - 1, p, p, p, p,
+              None) == ARG
+    for b, h, w in ((1, 1, 1), (2, 1, 255), (3, 1, 256), (3, 1, 257), (1, 3, 171), (2, 257, 257), (65, 363, 363)):
+        want = -(-b * 4 // 256) * 256 + b * -(-h * w // 256) * 2 * 4
+        assert lib.tmvs_entropy_loss_workspace(b, h, w) == want, (b, h, w)
+    for dims in ((0, 8, 8), (1, 0, 8), (1, 8, 0), (-1, 8, 8)):
+        assert lib.tmvs_entropy_loss_workspace(*dims) == 0, dims
+
+    ad, add = lib.tmvs_adam_step, lib.tmvs_adam_step_dev
+    hyper = (1e-3, 0.9, 0.999, 1e-8, 1e-4)
+    for nul in range(4):
+        a = [p] * 4
+        a[nul] = None
+        assert ad(*a, 16, *hyper, 1, None) == ARG, nul
+    for n, step in ((0, 1), (-1, 1), (16, 0), (16, -1)):
+        assert ad(p, p, p, p, n, *hyper, step, None) == ARG, (n, step)
+    for nul in range(6):  # lr_dev is optional
+        a = [p] * 6
+        a[nul] = None
+        assert add(a[0], a[1], a[2], a[3], 16, hyper[0], None, *hyper[1:], a[4], a[5], None) == ARG, nul
+    for n in (0, -1):
+        assert add(p, p, p, p, n, hyper[0], None, *hyper[1:], p, p, None) == ARG, n
+
+
 def test_training_conv_bn_validation_without_gpu(lib):
     """The training convolution, weight-gradient and BatchNorm entry points (costreg_train / featurenet_train):
     null pointers and non-positive extents are TMVS_ERR_ARG, channel counts outside the dispatch tables,

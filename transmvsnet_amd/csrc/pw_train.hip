@@ -165,11 +165,14 @@ __global__ __launch_bounds__(kPwBlock) void aggregate_train_kernel(const float* 
 }
 
 // ---------------------------------------------------------------- backward
-// dsims[v][d][p] = dsim[d][p] / wsum[p] * w_v[p]; dw_v[p] = sum_d dsim/wsum * (sims_v - sim)  (dw optional)
+// dsims[v][d][p] = dsim[d][p] / wsum[p] * w_v[p]; dw_v[p] = sum_d dsim/wsum * (sims_v - sim)  (dw optional).
+// sims_v - sim is formed as (sims_v * W - sum_u w_u sims_u) / W in fp64, W = 1e-5 + sum_u w_u, where every
+// product is exact: subtracting the forward's rounded sim loses the difference to rounding wherever one view
+// carries nearly all the weight (a single view: sims - sim = 1e-5 sims / W, below sim's last bits).
 __global__ __launch_bounds__(kPwBlock) void aggregate_backward_kernel(
-    const float* __restrict__ dsim, const float* __restrict__ sims, const float* __restrict__ sim,
-    const float* __restrict__ wsum, const float* __restrict__ w, int V, int D, int H, int W, int shift,
-    float* __restrict__ dsims, float* __restrict__ dw) {
+    const float* __restrict__ dsim, const float* __restrict__ sims, const float* __restrict__ wsum,
+    const float* __restrict__ w, int V, int D, int H, int W, int shift, float* __restrict__ dsims,
+    float* __restrict__ dw) {
   const int P = H * W;
   const int q = blockIdx.x * kPwBlock + threadIdx.x;
   if (q >= P) return;
@@ -177,16 +180,23 @@ __global__ __launch_bounds__(kPwBlock) void aggregate_backward_kernel(
   const int Ws = W >> shift, Ps = (H >> shift) * Ws;
   const int qs = (y >> shift) * Ws + (x >> shift);
   const float ws = wsum[q];
+  double wd = (double)1e-5f;
+  if (dw)
+    for (int v = 0; v < V; ++v) wd += (double)w[(size_t)v * Ps + qs];
   for (int v = 0; v < V; ++v) {
     const float wv = w[(size_t)v * Ps + qs];
-    float acc = 0.f;
+    double acc = 0.0;
     for (int d = 0; d < D; ++d) {
       const float g = dsim[(size_t)d * P + q] / ws;
       const size_t e = ((size_t)v * D + d) * P + q;
       dsims[e] = g * wv;
-      if (dw) acc = fmaf(g, sims[e] - sim[(size_t)d * P + q], acc);
+      if (dw) {
+        double a = 0.0;
+        for (int u = 0; u < V; ++u) a += (double)w[(size_t)u * Ps + qs] * (double)sims[((size_t)u * D + d) * P + q];
+        acc += (double)g * ((double)sims[e] * wd - a);
+      }
     }
-    if (dw) dw[(size_t)v * P + q] = acc;
+    if (dw) dw[(size_t)v * P + q] = (float)(acc / wd);
   }
 }
 
@@ -332,6 +342,13 @@ __global__ void pw_grad_finalize_kernel(const double* __restrict__ s1, const dou
 // element / pixel ranges of the partial passes: at most the 1024 blocks the workspace holds
 static Chunk pw_chunk(long n) { return chunk_for(n, 1024, 1024); }
 
+// the aggregate kernels read view_w at (y >> shift, x >> shift) of an [H >> shift][W >> shift] map: a
+// remainder would put the last column on the next row's weight and the last row past the view's map
+constexpr int kMaxVwShift = 4;
+static bool vw_map_covers(int height, int width, int shift) {
+  return shift <= kMaxVwShift && !(height & ((1 << shift) - 1)) && !(width & ((1 << shift) - 1));
+}
+
 }  // namespace tmvs
 
 using namespace tmvs;
@@ -372,6 +389,7 @@ extern "C" int tmvs_aggregate_train(const float* sims, const float* view_w, int 
                                     int width, int vw_shift, float* sim, float* wsum, void* stream) {
   if (!sims || !view_w || !sim || !wsum || n_views <= 0 || ndepth <= 0 || height <= 0 || width <= 0 || vw_shift < 0)
     return TMVS_ERR_ARG;
+  if (!vw_map_covers(height, width, vw_shift)) return TMVS_ERR_SHAPE;
   const int P = height * width;
   hipLaunchKernelGGL(aggregate_train_kernel, dim3((P + kPwBlock - 1) / kPwBlock), dim3(kPwBlock), 0,
                      (hipStream_t)stream, sims, view_w, n_views, ndepth, height, width, vw_shift, sim, wsum);
@@ -385,10 +403,11 @@ extern "C" int tmvs_aggregate_train_backward(const float* dsim, const float* sim
   if (!dsim || !sims || !sim || !wsum || !view_w || !dsims || n_views <= 0 || ndepth <= 0 || height <= 0 ||
       width <= 0 || vw_shift < 0)
     return TMVS_ERR_ARG;
+  if (!vw_map_covers(height, width, vw_shift)) return TMVS_ERR_SHAPE;
   const int P = height * width;
   hipLaunchKernelGGL(aggregate_backward_kernel, dim3((P + kPwBlock - 1) / kPwBlock), dim3(kPwBlock), 0,
-                     (hipStream_t)stream, dsim, sims, sim, wsum, view_w, n_views, ndepth, height, width, vw_shift,
-                     dsims, dview_w);
+                     (hipStream_t)stream, dsim, sims, wsum, view_w, n_views, ndepth, height, width, vw_shift, dsims,
+                     dview_w);  // sim: required by the ABI, no longer read
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }

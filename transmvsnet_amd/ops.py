@@ -602,11 +602,13 @@ def conv2d_bn_relu(x, w_packed, cout, k, stride, bn=None, relu=True, nchw_input=
     return out
 
 
-def entropy_loss(prob, depth_values, depth_gt, mask, grad_scale=0.0, want_grad=False):
+def entropy_loss(prob, depth_values, depth_gt, mask, grad_scale=0.0, want_grad=False, wta=None, conf=None, grad=None):
     """One stage's entropy_loss (models/module.py:495-531) + smooth-L1 depth loss (:549), and with
     want_grad the gradient of grad_scale * loss w.r.t. the stage's softmax logits.
-    Returns (loss [], depth_loss [], wta_depth [B,H,W], photo_conf [B,H,W], grad_logits or None)."""
-    for t, n in ((prob, "prob"), (depth_values, "depth_values"), (depth_gt, "depth_gt"), (mask, "mask")):
+    Returns (loss [], depth_loss [], wta_depth [B,H,W], photo_conf [B,H,W], grad_logits or None).
+    wta / conf / grad: caller-provided contiguous outputs of those shapes (grad only with want_grad)."""
+    for t, n in ((prob, "prob"), (depth_values, "depth_values"), (depth_gt, "depth_gt"), (mask, "mask"),
+                 (wta, "wta"), (conf, "conf"), (grad, "grad")):
         _dev(t, n)
     b, d, h, w = prob.shape
     if depth_values.dim() == 4:
@@ -622,9 +624,15 @@ def entropy_loss(prob, depth_values, depth_gt, mask, grad_scale=0.0, want_grad=F
     nbytes = _lib_h().tmvs_entropy_loss_workspace(b, h, w)
     ws = torch.empty(nbytes // 4 + 64, device=prob.device)
     out = torch.empty(2, device=prob.device)
-    wta = torch.empty(b, h, w, device=prob.device)
-    conf = torch.empty_like(wta)
-    grad = torch.empty_like(prob) if want_grad else None
+    if grad is not None and not want_grad:
+        raise ValueError("entropy_loss: grad given without want_grad")
+    wta = torch.empty(b, h, w, device=prob.device) if wta is None else wta
+    conf = torch.empty(b, h, w, device=prob.device) if conf is None else conf
+    if want_grad and grad is None:
+        grad = torch.empty_like(prob)
+    for t, n, shape in ((wta, "wta", (b, h, w)), (conf, "conf", (b, h, w)), (grad, "grad", (b, d, h, w))):
+        if t is not None and (tuple(t.shape) != shape or t.device != prob.device):
+            raise ValueError(f"entropy_loss: {n} must be a contiguous {list(shape)} tensor on prob's device")
     with _Span("tmvs_entropy_loss"):
         _lib.check(_lib_h().tmvs_entropy_loss(_ptr(prob), _ptr(depth_values), per_pixel, _ptr(depth_gt), _ptr(mask), b,
                                               d, h, w, ctypes.c_float(grad_scale), _ptr(ws), ws.numel() * 4,
@@ -877,11 +885,39 @@ def warp_corr_backward(ref_nhwc, src_nhwc, proj12, hyp, dsim, rot_order="auto", 
     return dref, dsrc, flag
 
 
+def _pw_shaped(op, t, name, shape, like, dtype=torch.float32):
+    """`t` is a contiguous `dtype` tensor of `shape` on `like`'s device: the PixelwiseNet / aggregation entry
+    points take one V, D, H, W for all their tensors and would read or write any other size past its end"""
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != like.device
+            or tuple(t.shape) != tuple(shape)):
+        kind = "int32" if dtype == torch.int32 else "float32"
+        got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{op}: {name} must be a contiguous {kind} {list(shape)} tensor on sims' device, not {got}")
+
+
+def _pw_sims(op, sims):
+    _dev(sims, "sims")
+    if sims.dim() != 4:
+        raise ValueError(f"{op}: sims must be [V, D, H, W], not {list(sims.shape)}")
+    return sims.shape
+
+
+def _vw_map_shape(op, v, h, w, vw_shift):
+    """[V, H >> s, W >> s]: the map the aggregate kernels read at (y >> s, x >> s), which covers the image only
+    when H and W are multiples of 2^s"""
+    s = int(vw_shift)
+    if not 0 <= s <= 4:
+        raise ValueError(f"{op}: vw_shift must be in [0, 4], not {vw_shift}")
+    if h % (1 << s) or w % (1 << s):
+        raise ValueError(f"{op}: H = {h} and W = {w} must be multiples of 2^vw_shift = {1 << s}")
+    return (v, h >> s, w >> s)
+
+
 def pixelwise_train_forward(sims, pwp):
     """tmvs_pixelwise_train_forward: sims [V,D,H,W], pwp [201] -> (stats [V,48], view_w [V,H,W], dstar int32)."""
-    _dev(sims, "sims")
-    _dev(pwp, "pwp")
-    v, d, h, w = sims.shape
+    op = "pixelwise_train_forward"
+    v, d, h, w = _pw_sims(op, sims)
+    _pw_shaped(op, pwp, "pwp", (_lib.PW_NPARAMS,), sims)
     ws = torch.empty(_lib_h().tmvs_pixelwise_train_workspace() // 4 + 64, device=sims.device)
     stats = torch.empty(v, 48, device=sims.device)
     vw = torch.empty(v, h, w, device=sims.device)
@@ -893,12 +929,15 @@ def pixelwise_train_forward(sims, pwp):
     return stats, vw, dstar
 
 
-def aggregate_train(sims, view_w, vw_shift):
-    """tmvs_aggregate_train: sims [V,D,H,W], view_w [V,H>>s,W>>s] -> (sim [D,H,W], wsum [H,W])."""
-    _dev(sims, "sims")
-    _dev(view_w, "view_w")
-    v, d, h, w = sims.shape
-    sim = torch.empty(d, h, w, device=sims.device)
+def aggregate_train(sims, view_w, vw_shift, sim=None):
+    """tmvs_aggregate_train: sims [V,D,H,W], view_w [V,H>>s,W>>s] -> (sim [D,H,W], wsum [H,W]).
+    sim: a caller-provided contiguous [D,H,W] output."""
+    op = "aggregate_train"
+    v, d, h, w = _pw_sims(op, sims)
+    _pw_shaped(op, view_w, "view_w", _vw_map_shape(op, v, h, w, vw_shift), sims)
+    if sim is None:
+        sim = torch.empty(d, h, w, device=sims.device)
+    _pw_shaped(op, sim, "sim", (d, h, w), sims)
     wsum = torch.empty(h, w, device=sims.device)
     with _Span("tmvs_aggregate_train"):
         _lib.check(_lib_h().tmvs_aggregate_train(_ptr(sims), _ptr(view_w), v, d, h, w, vw_shift, _ptr(sim), _ptr(wsum),
@@ -906,28 +945,40 @@ def aggregate_train(sims, view_w, vw_shift):
     return sim, wsum
 
 
-def aggregate_train_backward(dsim, sims, sim, wsum, view_w, vw_shift, want_dview_w):
-    """tmvs_aggregate_train_backward -> (dsims [V,D,H,W], dview_w [V,H,W] or None)."""
-    for t, n in ((dsim, "dsim"), (sims, "sims"), (sim, "sim"), (wsum, "wsum"), (view_w, "view_w")):
-        _dev(t, n)
-    v, d, h, w = sims.shape
-    dsims = torch.empty_like(sims)
-    dvw = torch.empty(v, h, w, device=sims.device) if want_dview_w else None
+def aggregate_train_backward(dsim, sims, sim, wsum, view_w, vw_shift, want_dview_w, dsims=None, dview_w=None):
+    """tmvs_aggregate_train_backward -> (dsims [V,D,H,W], dview_w [V,H,W] or None).
+    dsims / dview_w: caller-provided contiguous outputs of those shapes (dview_w only with want_dview_w)."""
+    op = "aggregate_train_backward"
+    v, d, h, w = _pw_sims(op, sims)
+    _pw_shaped(op, view_w, "view_w", _vw_map_shape(op, v, h, w, vw_shift), sims)
+    for t, n, shape in ((dsim, "dsim", (d, h, w)), (sim, "sim", (d, h, w)), (wsum, "wsum", (h, w))):
+        _pw_shaped(op, t, n, shape, sims)
+    if dview_w is not None and not want_dview_w:
+        raise ValueError(f"{op}: dview_w given without want_dview_w")
+    if dsims is None:
+        dsims = torch.empty_like(sims)
+    if want_dview_w and dview_w is None:
+        dview_w = torch.empty(v, h, w, device=sims.device)
+    _pw_shaped(op, dsims, "dsims", (v, d, h, w), sims)
+    if want_dview_w:
+        _pw_shaped(op, dview_w, "dview_w", (v, h, w), sims)
     with _Span("tmvs_aggregate_train_backward"):
         _lib.check(_lib_h().tmvs_aggregate_train_backward(_ptr(dsim), _ptr(sims), _ptr(sim), _ptr(wsum), _ptr(view_w), v,
-                                                          d, h, w, vw_shift, _ptr(dsims), _ptr(dvw), _stream()),
+                                                          d, h, w, vw_shift, _ptr(dsims), _ptr(dview_w), _stream()),
                    "tmvs_aggregate_train_backward")
-    return dsims, dvw
+    return dsims, dview_w
 
 
 def pixelwise_train_backward(sims, pwp, stats, view_w, dstar, dview_w, dsims):
     """tmvs_pixelwise_train_backward: adds the PixelwiseNet path into dsims (in place) -> dpwp [201]."""
-    for t, n in ((sims, "sims"), (pwp, "pwp"), (stats, "stats"), (view_w, "view_w"), (dview_w, "dview_w"),
-                 (dsims, "dsims")):
-        _dev(t, n)
-    v, d, h, w = sims.shape
+    op = "pixelwise_train_backward"
+    v, d, h, w = _pw_sims(op, sims)
+    for t, n, shape in ((pwp, "pwp", (_lib.PW_NPARAMS,)), (stats, "stats", (v, 48)), (view_w, "view_w", (v, h, w)),
+                        (dview_w, "dview_w", (v, h, w)), (dsims, "dsims", (v, d, h, w))):
+        _pw_shaped(op, t, n, shape, sims)
+    _pw_shaped(op, dstar, "dstar", (v, h, w), sims, torch.int32)
     ws = torch.empty(_lib_h().tmvs_pixelwise_train_workspace() // 4 + 64, device=sims.device)
-    dpwp = torch.zeros(201, device=sims.device)
+    dpwp = torch.zeros(_lib.PW_NPARAMS, device=sims.device)
     with _Span("tmvs_pixelwise_train_backward"):
         _lib.check(_lib_h().tmvs_pixelwise_train_backward(_ptr(sims), v, d, h, w, _ptr(pwp), _ptr(stats), _ptr(view_w),
                                                           _ptr(dstar), _ptr(dview_w), _ptr(ws), ws.numel() * 4,
