@@ -14,11 +14,11 @@
 //   v  = fmaf(se_v,se, fmaf(sw_v,sw, fmaf(ne_v,ne, nw_v*nw)))  (zeros padding)
 //   sim = (Σ_c v_c*ref_c) / C ; sim_sum += sim*w ; w_sum = 1e-5 + Σ w ; sim_sum / w_sum
 // (the channel sum: serial within each lane's 4 channels, then a fixed xor tree over lanes)
+#include <utility>
+
 #include "common.h"
 
 namespace tmvs {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct WarpArgs {
   float proj[TMVS_MAX_VIEWS][12];
@@ -31,6 +31,49 @@ struct WarpArgs {
 // not on AMD EPYC (measured, scripts/diag/warp_bits.py); the coordinate then differs by up to 1.2e-4.
 __device__ __forceinline__ float rot_row(const float* R, float x, float y, int plain) {
   return plain ? (R[0] * x + R[1] * y) + R[2] : fmaf(R[1], y, R[0] * x) + R[2];
+}
+
+// rot·(x, y, 1) of reference pixel (x, y) under the 3x4 projection R: the ray that every depth plane scales.
+// The helpers of this unit keep the statement order of the code they replaced, and pixel_ray fills a
+// reference rather than returning the struct: the compiler's schedule follows both, and either change
+// moved instructions in the forward kernels (profiles/warp_scaffold_resources.md).
+struct Ray {
+  float x, y, z;
+};
+__device__ __forceinline__ void pixel_ray(const float* R, float x, float y, int plain, Ray& r) {
+  r.x = rot_row(R, x, y, plain);
+  r.y = rot_row(R + 4, x, y, plain);
+  r.z = rot_row(R + 8, x, y, plain);
+}
+
+// A sample's bilinear footprint: its north-west tap and the fractions towards the east and south taps
+struct Geom {
+  int x0, y0;
+  float fx, fy;
+};
+
+// The ray's point at depth dep in the source image, (tx, ty, tz) = R[3], R[7], R[11]
+__device__ __forceinline__ Geom project(const Ray& r, float tx, float ty, float tz, float dep, float halfw,
+                                        float halfh) {
+  const float X = r.x * dep + tx;
+  const float Y = r.y * dep + ty;
+  const float Z = r.z * dep + tz;
+  float xn = (X / Z) / halfw - 1.f;
+  float yn = (Y / Z) / halfh - 1.f;
+  if (Z < 1e-6f) {
+    xn = -99.f;
+    yn = -99.f;
+  }
+  const float ix = (xn + 1.f) * halfw;
+  const float iy = (yn + 1.f) * halfh;
+  const float x0 = floorf(ix), y0 = floorf(iy);
+  Geom g;
+  g.fx = ix - x0;
+  g.fy = iy - y0;
+  // clamp far-away samples (all four taps outside) to a sentinel that stays outside
+  g.x0 = (int)fminf(fmaxf(x0, -2.f), 32766.f);
+  g.y0 = (int)fminf(fmaxf(y0, -2.f), 32766.f);
+  return g;
 }
 
 __device__ __forceinline__ float pixelwise_logit(float s, const float* __restrict__ pw) {
@@ -82,40 +125,15 @@ __device__ __forceinline__ float pixelwise_logit(float s, const float* __restric
 // several instructions, or mixes planes inside a group, costs up to 2x). All rounds' loads
 // are issued before any is consumed; a butterfly reduce-scatter then gives lane t the full
 // channel sum of plane t.
-__device__ __forceinline__ void project(const float rx, const float ry, const float rz, const float tx,
-                                        const float ty, const float tz, const float dep, const float halfw,
-                                        const float halfh, int& x0i, int& y0i, float& fx, float& fy) {
-  const float X = rx * dep + tx;
-  const float Y = ry * dep + ty;
-  const float Z = rz * dep + tz;
-  float xn = (X / Z) / halfw - 1.f;
-  float yn = (Y / Z) / halfh - 1.f;
-  if (Z < 1e-6f) {
-    xn = -99.f;
-    yn = -99.f;
-  }
-  const float ix = (xn + 1.f) * halfw;
-  const float iy = (yn + 1.f) * halfh;
-  const float x0 = floorf(ix), y0 = floorf(iy);
-  fx = ix - x0;
-  fy = iy - y0;
-  // clamp far-away samples (all four taps outside) to a sentinel that stays outside
-  x0i = (int)fminf(fmaxf(x0, -2.f), 32766.f);
-  y0i = (int)fminf(fmaxf(y0, -2.f), 32766.f);
-}
 
-// x from lane (lane ^ R) inside an aligned group of 8 (R compile-time)
-template <int R>
-__device__ __forceinline__ int lane_xor(int x) {
-  if constexpr (R == 0) return x;
-  else if constexpr (R == 1) return __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
-  else if constexpr (R == 2) return __builtin_amdgcn_mov_dpp(x, 0x4E, 0xF, 0xF, false);  // quad_perm [2,3,0,1]
-  else if constexpr (R == 3) return __builtin_amdgcn_mov_dpp(x, 0x1B, 0xF, 0xF, false);  // quad_perm [3,2,1,0]
-  else return __builtin_amdgcn_ds_swizzle(x, 0x1F | (R << 10));                           // bit mode, xor R
-}
+// x from lane (lane ^ R) inside an aligned group of 8 (R = 1, 2 or 4)
 template <int R>
 __device__ __forceinline__ float lane_xor_f(float x) {
-  return __int_as_float(lane_xor<R>(__float_as_int(x)));
+  static_assert(R == 1 || R == 2 || R == 4, "xor distance inside a group of 8");
+  const int i = __float_as_int(x);
+  if constexpr (R == 1) return __int_as_float(__builtin_amdgcn_mov_dpp(i, 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
+  else if constexpr (R == 2) return __int_as_float(__builtin_amdgcn_mov_dpp(i, 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
+  else return __int_as_float(__builtin_amdgcn_ds_swizzle(i, 0x1F | (R << 10)));  // bit mode, xor R
 }
 
 template <int LPS>
@@ -126,392 +144,10 @@ __device__ __forceinline__ float group_max(float v) {
   return v;
 }
 
-// Buffer resource over one sample's source views: raw (stride 0) addressing with 32-bit byte
-// offsets. An offset at or past num_records reads as 0 -- exactly grid_sample's zero padding --
-// so an out-of-image tap only needs an out-of-range offset: each axis term is kAxisOut when
-// invalid, and any sum containing one is >= kAxisOut >= num_records (< 2^30, checked).
-constexpr unsigned kAxisOut = 0x40000000u;
-
-struct Geom {
-  int x0, y0;
-  float fx, fy;
-};
-
-// x from lane t of this lane's aligned group of LPS lanes (t compile-time): the group's
-// lanes all receive the same value -- DPP quad permutes for LPS <= 4, ds_swizzle (bit mode,
-// no memory access) for LPS = 8
-template <int LPS, int T>
-__device__ __forceinline__ int group_bcast(int x) {
-  if constexpr (LPS == 1) return x;
-  else if constexpr (LPS == 2) return __builtin_amdgcn_mov_dpp(x, T | (T << 2) | ((T + 2) << 4) | ((T + 2) << 6), 0xF, 0xF, false);
-  else if constexpr (LPS == 4) return __builtin_amdgcn_mov_dpp(x, T * 0x55, 0xF, 0xF, false);
-  else return __builtin_amdgcn_ds_swizzle(x, 0x18 | (T << 5));  // lane' = (lane & 0x18) | T
-}
-
-template <int LPS, int T>
-__device__ __forceinline__ Geom geom_bcast(const Geom& g) {
-  return Geom{group_bcast<LPS, T>(g.x0), group_bcast<LPS, T>(g.y0),
-              __int_as_float(group_bcast<LPS, T>(__float_as_int(g.fx))),
-              __int_as_float(group_bcast<LPS, T>(__float_as_int(g.fy)))};
-}
-
-
-// Tap reuse across consecutive planes. A pixel's depth planes project to nearby points on the
-// epipolar line, so consecutive planes mostly share bilinear taps (unique taps per pixel-view,
-// synthetic DTU rig: 129 / 48 / 14 of 192 / 128 / 32 tap loads in stages 1 / 2 / 3). The 4
-// taps of a plane always occupy the 4 (x parity, y parity) classes, so tap (X, Y) is cached in
-// register slot (X&1, Y&1) with its position as tag: a plane loads only the slots whose tag
-// changed. The address unit's cost scales with the lanes that make a memory request (measured,
-// scripts/micro/ta_mask.hip: exec-masked and out-of-range lanes are equally free), so skipped
-// loads are skipped work.
-struct Slots {
-  floatx4 v[4];
-  unsigned pos[4];
-};
-
-__device__ __forceinline__ void slots_reset(Slots& S) {
-#pragma unroll
-  for (int s = 0; s < 4; ++s) S.pos[s] = 0xFFFFFFFFu;  // no position packs to this
-}
-
-template <int C>
-__device__ __forceinline__ void fetch_reuse(const __amdgpu_buffer_rsrc_t rsrc, unsigned vbase, unsigned rowb, int W,
-                                            int H, const Geom& g, Slots& S, floatx4 (&val)[4], float (&w)[4]) {
-  constexpr unsigned CB = C * 4;
-  const float we = g.fx, n = g.fy;
-  const float ea = 1.f - we, s = 1.f - n;
-#pragma unroll
-  for (int sl = 0; sl < 4; ++sl) {
-    const int px = sl & 1, py = sl >> 1;
-    const int X = g.x0 + ((g.x0 ^ px) & 1), Y = g.y0 + ((g.y0 ^ py) & 1);
-    const unsigned key = (unsigned)(X + 2) | ((unsigned)(Y + 2) << 16);  // X, Y in [-2, 32767]
-    // branch-free: a lane whose slot still holds the tap issues the load with an out-of-range
-    // offset (no memory request; costs the address unit what an exec-masked lane costs, measured)
-    const bool need = key != S.pos[sl];
-    S.pos[sl] = key;
-    const bool inside = (unsigned)X < (unsigned)W && (unsigned)Y < (unsigned)H;  // outside: reads 0
-    const unsigned off = (need && inside) ? vbase + (unsigned)Y * rowb + (unsigned)X * CB : kOffOut;
-    const floatx4 ld = buf_load_f32x4(rsrc, off);
-    S.v[sl] = need ? ld : S.v[sl];
-    val[sl] = S.v[sl];
-    // grid_sample's weights: (y weight) * (x weight), nw = (1-fy)(1-fx) ...
-    w[sl] = ((Y == g.y0) ? s : n) * ((X == g.x0) ? ea : we);
-  }
-}
-
-// Without the cache (stage 1: uniform planes ~1.4 px apart share few taps): the 4 taps in
-// grid_sample's order nw, ne, sw, se, so the interpolation's fma chain is the reference's.
-template <int C>
-__device__ __forceinline__ void fetch_full(const __amdgpu_buffer_rsrc_t rsrc, unsigned vbase, unsigned rowb, int W,
-                                           int H, const Geom& g, floatx4 (&val)[4], float (&w)[4]) {
-  constexpr unsigned CB = C * 4;
-  const float we = g.fx, n = g.fy;
-  const float ea = 1.f - we, s = 1.f - n;
-  w[0] = s * ea;
-  w[1] = s * we;
-  w[2] = n * ea;
-  w[3] = n * we;
-  const unsigned xa = (unsigned)g.x0 < (unsigned)W ? (unsigned)g.x0 * CB : kAxisOut;
-  const unsigned xb = (unsigned)(g.x0 + 1) < (unsigned)W ? (unsigned)(g.x0 + 1) * CB : kAxisOut;
-  const unsigned yrow = vbase + (unsigned)g.y0 * rowb;
-  const unsigned ya = (unsigned)g.y0 < (unsigned)H ? yrow : kAxisOut;
-  const unsigned yb = (unsigned)(g.y0 + 1) < (unsigned)H ? yrow + rowb : kAxisOut;
-  val[0] = buf_load_f32x4(rsrc, ya + xa);
-  val[1] = buf_load_f32x4(rsrc, ya + xb);
-  val[2] = buf_load_f32x4(rsrc, yb + xa);
-  val[3] = buf_load_f32x4(rsrc, yb + xb);
-}
-
-// bilinear value of each channel (fixed slot order), times ref, summed in channel order
-__device__ __forceinline__ float combine(const floatx4 (&v)[4], const float (&w)[4], const float4& r4) {
-  float acc = 0.f;
-  acc = acc + fmaf(v[3][0], w[3], fmaf(v[2][0], w[2], fmaf(v[1][0], w[1], v[0][0] * w[0]))) * r4.x;
-  acc = acc + fmaf(v[3][1], w[3], fmaf(v[2][1], w[2], fmaf(v[1][1], w[1], v[0][1] * w[0]))) * r4.y;
-  acc = acc + fmaf(v[3][2], w[3], fmaf(v[2][2], w[2], fmaf(v[1][2], w[1], v[0][2] * w[0]))) * r4.z;
-  acc = acc + fmaf(v[3][3], w[3], fmaf(v[2][3], w[2], fmaf(v[1][3], w[1], v[0][3] * w[0]))) * r4.w;
-  return acc;
-}
-
-// Rounds R0..R0+N-1: in round t the whole group samples plane slot t (geometry broadcast from
-// lane t), so each load instruction covers one contiguous C*4-byte row per group. Every
-// round's (masked) loads are issued before any is consumed.
-template <int C, bool REUSE, int R0, int N>
-__device__ __forceinline__ void rounds(const __amdgpu_buffer_rsrc_t rsrc, unsigned vbase, unsigned rowb, int W,
-                                       int H, const Geom& own, const float4& r4, Slots& S, float* part) {
-  floatx4 v[N][4];
-  float w[N][4];
-#define TMVS_FETCH(I)                                                                          \
-  if constexpr (REUSE)                                                                         \
-    fetch_reuse<C>(rsrc, vbase, rowb, W, H, geom_bcast<C / 4, R0 + I>(own), S, v[I], w[I]); \
-  else                                                                                         \
-    fetch_full<C>(rsrc, vbase, rowb, W, H, geom_bcast<C / 4, R0 + I>(own), v[I], w[I]);
-  TMVS_FETCH(0)
-  if constexpr (N > 1) { TMVS_FETCH(1) }
-  if constexpr (N > 2) { TMVS_FETCH(2) }
-  if constexpr (N > 3) { TMVS_FETCH(3) }
-#undef TMVS_FETCH
-#pragma unroll
-  for (int i = 0; i < N; ++i) part[R0 + i] = combine(v[i], w[i], r4);
-}
-
-// Full channel sum of this lane's own plane (slot k): LPS rounds, then a butterfly
-// reduce-scatter over lane bits (xor 4, xor 2, xor 1). At each step a lane keeps the half of
-// the planes whose slot bit matches its own lane bit and sends the other half to its partner;
-// the sum for slot t ends in lane t: no dependent shuffle chains, LPS-1 exchanges.
-template <int C, bool REUSE>
-__device__ __forceinline__ float plane_corr(const __amdgpu_buffer_rsrc_t rsrc, unsigned vbase, unsigned rowb, int W,
-                                            int H, const Geom& own, const float4& r4, int k, Slots& S) {
-  constexpr int LPS = C / 4;
-  float p[LPS];
-  if constexpr (REUSE) {
-    // batches of 2 rounds: the cached slots plus a batch's loads fit the VGPR budget
-    rounds<C, true, 0, 2>(rsrc, vbase, rowb, W, H, own, r4, S, p);
-    if constexpr (LPS >= 4) {
-      __builtin_amdgcn_sched_barrier(0);
-      rounds<C, true, 2, 2>(rsrc, vbase, rowb, W, H, own, r4, S, p);
-    }
-    if constexpr (LPS >= 8) {
-      __builtin_amdgcn_sched_barrier(0);
-      rounds<C, true, 4, 2>(rsrc, vbase, rowb, W, H, own, r4, S, p);
-      __builtin_amdgcn_sched_barrier(0);
-      rounds<C, true, 6, 2>(rsrc, vbase, rowb, W, H, own, r4, S, p);
-    }
-  } else if constexpr (LPS <= 4) {
-    rounds<C, false, 0, LPS>(rsrc, vbase, rowb, W, H, own, r4, S, p);
-  } else {
-    rounds<C, false, 0, 4>(rsrc, vbase, rowb, W, H, own, r4, S, p);
-    rounds<C, false, 4, 4>(rsrc, vbase, rowb, W, H, own, r4, S, p);
-  }
-  float q[LPS];
-#pragma unroll
-  for (int i = 0; i < LPS; ++i) q[i] = p[i];
-  int n = LPS;
-  if constexpr (LPS >= 8) {
-    const bool hi = (k & 4) != 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float keep = hi ? q[4 + i] : q[i], send = hi ? q[i] : q[4 + i];
-      q[i] = keep + lane_xor_f<4>(send);
-    }
-    n = 4;
-  }
-  if constexpr (LPS >= 4) {
-    const bool hi = (k & 2) != 0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float keep = hi ? q[2 + i] : q[i], send = hi ? q[i] : q[2 + i];
-      q[i] = keep + lane_xor_f<2>(send);
-    }
-    n = 2;
-  }
-  (void)n;
-  if constexpr (LPS >= 2) {
-    const bool hi = (k & 1) != 0;
-    const float keep = hi ? q[1] : q[0], send = hi ? q[0] : q[1];
-    q[0] = keep + lane_xor_f<1>(send);
-  }
-  return q[0];
-}
-
-// Views outer (a view's consecutive planes hit the same source lines: L1 reuse), planes inner
-// and not unrolled: the plane's depth and running weighted sum live in this thread's LDS
-// column, so the rounds' independent loads are the only large live set.
-template <int C, int D, bool PW, bool PARTIAL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void warp_corr_kernel(
-    const float* __restrict__ ref, const float* __restrict__ src, const float* __restrict__ hyp,
-    const float* __restrict__ vw_in, float* __restrict__ sim_out, float* __restrict__ wsum_out,
-    float* __restrict__ vw_out, int V, int H, int W, int vw_shift, int vw_offset, int vw_total, WarpArgs args) {
-  constexpr int LPS = C / 4;          // lanes per pixel
-  constexpr int SPW = 64 / LPS;       // pixels per wave
-  constexpr int PIX = 4 * SPW;        // pixels per block
-  constexpr int DPT = D / LPS;        // depth planes owned per lane
-  static_assert(D % LPS == 0, "D must be a multiple of C/4");
-  // PixelwiseNet parameters in LDS (uniform-address reads broadcast); as kernel arguments
-  // they would occupy ~200 SGPRs and spill
-  __shared__ __attribute__((aligned(16))) float pw_lds[PW ? TMVS_PW_NPARAMS + 3 : 4];
-  __shared__ float dep_lds[DPT][256];
-  __shared__ float acc_lds[DPT][256];
-  __shared__ float sim_lds[PW ? DPT : 1][PW ? 256 : 1];
-  const int tid = threadIdx.x;
-  if constexpr (PW) {
-    if (tid < TMVS_PW_NPARAMS) pw_lds[tid] = args.pw[tid];
-  }
-  const int HW = H * W;
-  const int nblk = (HW + PIX - 1) / PIX;
-  const int tile = xcd_remap(blockIdx.x, nblk);
-  const int lane = tid & 63;
-  const int k = lane % LPS;
-  int p = tile * PIX + (tid >> 6) * SPW + lane / LPS;
-  const bool active = p < HW;
-  if (!active) p = HW - 1;
-  const int py = p / W, px = p - py * W;
-  const float fxp = (float)px, fyp = (float)py;
-  const float4 r4 = *reinterpret_cast<const float4*>(ref + (size_t)p * C + 4 * k);
-#pragma unroll
-  for (int j = 0; j < DPT; ++j) {
-    dep_lds[j][tid] = hyp[(size_t)(j * LPS + k) * HW + p];
-    acc_lds[j][tid] = 0.f;
-  }
-  if constexpr (PW) __syncthreads();  // pw_lds is shared; the columns are per thread
-  const float halfw = (float)(W - 1) / 2.f;
-  const float halfh = (float)(H - 1) / 2.f;
-  float wsum = PARTIAL ? 0.f : 1e-5f;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)src, (short)0, V * HW * C * 4, kRsrcWord3);
-  const unsigned rowb = (unsigned)W * C * 4;
-  const int Ws = W >> vw_shift, Hs = H >> vw_shift;
-
-  for (int v = 0; v < V; ++v) {
-    const float* R = args.proj[v];
-    const float rx = rot_row(R, fxp, fyp, args.rot_plain);
-    const float ry = rot_row(R + 4, fxp, fyp, args.rot_plain);
-    const float rz = rot_row(R + 8, fxp, fyp, args.rot_plain);
-    const unsigned vbase = (unsigned)(v * HW * C * 4 + 16 * k);
-    float w = 0.f;
-    if constexpr (!PW) w = vw_in[(size_t)(vw_offset + v) * Hs * Ws + (py >> vw_shift) * Ws + (px >> vw_shift)];
-    float wm = 0.f;  // PW: running max of sigmoid (> 0, so 0 is neutral)
-    Slots S;  // tap cache, valid within one view: planes j*LPS + t run in depth order
-    slots_reset(S);
-#pragma unroll 1
-    for (int j = 0; j < DPT; ++j) {
-      Geom own;
-      project(rx, ry, rz, R[3], R[7], R[11], dep_lds[j][tid], halfw, halfh, own.x0, own.y0, own.fx, own.fy);
-      const float sim = plane_corr<C, !PW>(rsrc, vbase, rowb, W, H, own, r4, k, S) * (1.f / (float)C);  // C = 2^n: == / C
-      if constexpr (PW) {
-        sim_lds[j][tid] = sim;
-        int salt = 0;  // opaque offset: keeps the parameter reads from being hoisted into VGPRs
-        asm volatile("" : "+v"(salt));
-        const float lg = pixelwise_logit(sim, pw_lds + salt);
-        wm = fmaxf(wm, 1.f / (1.f + expf(-lg)));
-      } else {
-        acc_lds[j][tid] = acc_lds[j][tid] + sim * w;
-      }
-    }
-    if constexpr (PW) {
-      w = group_max<LPS>(wm);
-      if (active && k == 0) vw_out[(size_t)(vw_offset + v) * HW + p] = w;
-#pragma unroll 4
-      for (int j = 0; j < DPT; ++j) acc_lds[j][tid] = acc_lds[j][tid] + sim_lds[j][tid] * w;
-    }
-    wsum = wsum + w;
-  }
-  if (!active) return;
-#pragma unroll 4
-  for (int j = 0; j < DPT; ++j) {
-    const size_t o = (size_t)(j * LPS + k) * HW + p;
-    sim_out[o] = PARTIAL ? acc_lds[j][tid] : acc_lds[j][tid] / wsum;
-  }
-  if (PARTIAL && k == 0) wsum_out[p] = wsum;
-}
-
-__global__ void aggregate_finalize_kernel(float* __restrict__ sim, const float* __restrict__ wsum, int D, int HW) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= HW) return;
-  const float ws = 1e-5f + wsum[(size_t)blockIdx.y * HW + p];
-  float* s = sim + (size_t)blockIdx.y * D * HW + p;
-  for (int d = 0; d < D; ++d) s[(size_t)d * HW] = s[(size_t)d * HW] / ws;
-}
-
-// Materialising homo_warping for the reference seam: out [C][D][H][W] from NCHW src.
-__global__ void homo_warping_kernel(const float* __restrict__ src, const float* __restrict__ hyp,
-                                    float* __restrict__ out, int C, int D, int H, int W, WarpArgs args) {
-  const int HW = H * W;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= D * HW) return;
-  const int d = idx / HW, p = idx - d * HW;
-  const int py = p / W, px = p - py * W;
-  const float* R = args.proj[0];
-  const float fx = (float)px, fy = (float)py;
-  const float rx = rot_row(R, fx, fy, args.rot_plain);
-  const float ry = rot_row(R + 4, fx, fy, args.rot_plain);
-  const float rz = rot_row(R + 8, fx, fy, args.rot_plain);
-  const float dep = hyp[idx];
-  const float X = rx * dep + R[3], Y = ry * dep + R[7], Z = rz * dep + R[11];
-  const float halfw = (float)(W - 1) / 2.f, halfh = (float)(H - 1) / 2.f;
-  float xn = (X / Z) / halfw - 1.f, yn = (Y / Z) / halfh - 1.f;
-  if (Z < 1e-6f) {
-    xn = -99.f;
-    yn = -99.f;
-  }
-  const float ix = (xn + 1.f) * halfw, iy = (yn + 1.f) * halfh;
-  const float x0 = floorf(ix), y0 = floorf(iy);
-  const float we = ix - x0, ea = 1.f - we, n = iy - y0, s = 1.f - n;
-  const float wnw = s * ea, wne = s * we, wsw = n * ea, wse = n * we;
-  const bool vx0 = x0 >= 0.f && x0 <= (float)(W - 1), vx1 = x0 + 1.f >= 0.f && x0 + 1.f <= (float)(W - 1);
-  const bool vy0 = y0 >= 0.f && y0 <= (float)(H - 1), vy1 = y0 + 1.f >= 0.f && y0 + 1.f <= (float)(H - 1);
-  const int xi0 = vx0 ? (int)x0 : 0, xi1 = vx1 ? (int)x0 + 1 : 0;
-  const int yi0 = vy0 ? (int)y0 : 0, yi1 = vy1 ? (int)y0 + 1 : 0;
-  for (int c = 0; c < C; ++c) {
-    const float* sc = src + (size_t)c * HW;
-    const float a = (vy0 && vx0) ? sc[yi0 * W + xi0] : 0.f;
-    const float b = (vy0 && vx1) ? sc[yi0 * W + xi1] : 0.f;
-    const float cc = (vy1 && vx0) ? sc[yi1 * W + xi0] : 0.f;
-    const float dd = (vy1 && vx1) ? sc[yi1 * W + xi1] : 0.f;
-    out[(size_t)c * D * HW + idx] = fmaf(dd, wse, fmaf(cc, wsw, fmaf(b, wne, a * wnw)));
-  }
-}
-
-// C = 8 with given view weights (stage 3): "row pair" lane layout. A pixel is served by 4
-// lanes k = (tx, q): tx picks the tap column (x0 or x0+1), q the channel quad; in a round the
-// group's 4 lanes load one contiguous 64-byte span per tap row (x0 and x0+1, all 8 channels)
-// instead of two lanes loading 32-byte rows of different taps, so every lane quad of a load
-// instruction stays on one span (measured with the C/4 layout: 48 address-unit cycles per
-// instruction, stalled on the L1). Bilinear partial per lane: its column's two taps; the
-// reduce-scatter over the 4 lanes then adds the columns and the channel quads.
-// geometry of plane slot t (compile-time after unrolling) broadcast from lane t of the group
-template <int LPS>
-__device__ __forceinline__ Geom geom_round(const Geom& own, int t) {
-  if (t == 0) return geom_bcast<LPS, 0>(own);
-  if (t == 1) return geom_bcast<LPS, 1>(own);
-  if constexpr (LPS > 2) {
-    if (t == 2) return geom_bcast<LPS, 2>(own);
-    if (t == 3) return geom_bcast<LPS, 3>(own);
-  }
-  if constexpr (LPS > 4) {
-    if (t == 4) return geom_bcast<LPS, 4>(own);
-    if (t == 5) return geom_bcast<LPS, 5>(own);
-    if (t == 6) return geom_bcast<LPS, 6>(own);
-    return geom_bcast<LPS, 7>(own);
-  }
-  return own;
-}
-
-// Row-pair rounds R0..R0+N-1 (see warp_pair_kernel): in round t the group samples plane t;
-// this lane loads its tap column's two rows (one 16-byte channel quad each); all loads of the
-// batch are issued before any is consumed.
-template <int C, int R0, int N>
-__device__ __forceinline__ void pair_rounds(const __amdgpu_buffer_rsrc_t rsrc, unsigned vbase, unsigned rowb, int W,
-                                            int H, const Geom& own, const float4* r4, int tx, float* part) {
-  constexpr int LPS = C / 2;
-  floatx4 top[N], bot[N];
-  float wt[N], wb[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const Geom g = geom_round<LPS>(own, R0 + i);
-    const int X = g.x0 + tx;
-    const unsigned ox = (unsigned)X < (unsigned)W ? (unsigned)X * (unsigned)(C * 4) : kAxisOut;
-    const unsigned yrow = vbase + (unsigned)g.y0 * rowb;
-    const unsigned oa = (unsigned)g.y0 < (unsigned)H ? yrow : kAxisOut;
-    const unsigned ob = (unsigned)(g.y0 + 1) < (unsigned)H ? yrow + rowb : kAxisOut;
-    top[i] = buf_load_f32x4(rsrc, oa + ox);
-    bot[i] = buf_load_f32x4(rsrc, ob + ox);
-    const float wx = tx ? g.fx : 1.f - g.fx;
-    wt[i] = (1.f - g.fy) * wx;  // grid_sample: (y weight) * (x weight)
-    wb[i] = g.fy * wx;
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const float4 r = r4[R0 + i];
-    float acc = 0.f;
-    acc = acc + fmaf(bot[i][0], wb[i], top[i][0] * wt[i]) * r.x;
-    acc = acc + fmaf(bot[i][1], wb[i], top[i][1] * wt[i]) * r.y;
-    acc = acc + fmaf(bot[i][2], wb[i], top[i][2] * wt[i]) * r.z;
-    acc = acc + fmaf(bot[i][3], wb[i], top[i][3] * wt[i]) * r.w;
-    part[R0 + i] = acc;
-  }
-}
-
-// Butterfly reduce-scatter over a lane group (xor LPS/2 ... 1): lane k ends with slot k's sum.
+// Butterfly reduce-scatter over a lane group (xor LPS/2 ... 1): p[t] is this lane's partial of
+// plane slot t. At each step a lane keeps the half of the slots whose bit matches its own lane
+// bit and sends the other half to its partner; the sum for slot k ends in lane k: no dependent
+// shuffle chains, LPS-1 exchanges.
 template <int LPS>
 __device__ __forceinline__ float reduce_scatter(const float* p, int k) {
   float q[LPS];
@@ -541,17 +177,373 @@ __device__ __forceinline__ float reduce_scatter(const float* p, int k) {
   return q[0];
 }
 
-// Which samples share a load instruction. Plane-major rounds (the original layout): in round t the
-// wave's SPW groups sample SPW pixels at one plane each. Pixel-major rounds (used for C = 16): the
-// SPW groups sample PPR = SPW/LPS pixels × LPS consecutive planes each (stage 2:
-// 1 pixel × 8 planes), whose taps lie ≈0.7 px apart on one epipolar segment and so share cache lines.
-// Group g's round-t sample is owned by its lane t (geometry broadcast as before), so lane (g, k) owns
-// pixel k·PPR + g/LPS at planes j·LPS + g%LPS and holds the reference quads of the LPS pixels its
-// rounds visit. Each sample's arithmetic (lane roles, channel order, reduce-scatter) is unchanged:
-// the outputs are bit-identical either way. Measured (profiles/r13/warp_pmajor_ab.txt, two
-// alternating reps in one box): stage 2 345.1 -> 323.3 us, stage 3 247.2 -> 252.1 us (the address
-// unit is charged per 4-lane quad, so sharing lines between quads buys little); C = 8 keeps the
-// plane-major rounds.
+// The buffer resource over one sample's source views reads an offset at or past num_records
+// (< 2^30, checked by the entry point) as 0 -- exactly grid_sample's zero padding -- so an
+// out-of-image tap only needs an out-of-range offset. Where an offset is the sum of an x and a
+// y term, each term is kAxisOut when invalid: any sum containing one is >= 2^30 and cannot wrap
+// (two of common.h's kOffOut = 2^31 would wrap to an in-range 0, hence the second constant).
+constexpr unsigned kAxisOut = 0x40000000u;
+
+// x from lane t of this lane's aligned group of LPS lanes (t compile-time): the group's
+// lanes all receive the same value -- DPP quad permutes for LPS <= 4, ds_swizzle (bit mode,
+// no memory access) for LPS = 8
+template <int LPS, int T>
+__device__ __forceinline__ int group_bcast(int x) {
+  if constexpr (LPS == 1) return x;
+  else if constexpr (LPS == 2) return __builtin_amdgcn_mov_dpp(x, T | (T << 2) | ((T + 2) << 4) | ((T + 2) << 6), 0xF, 0xF, false);
+  else if constexpr (LPS == 4) return __builtin_amdgcn_mov_dpp(x, T * 0x55, 0xF, 0xF, false);
+  else return __builtin_amdgcn_ds_swizzle(x, 0x18 | (T << 5));  // lane' = (lane & 0x18) | T
+}
+
+template <int LPS, int T>
+__device__ __forceinline__ Geom geom_bcast(const Geom& g) {
+  return Geom{group_bcast<LPS, T>(g.x0), group_bcast<LPS, T>(g.y0),
+              __int_as_float(group_bcast<LPS, T>(__float_as_int(g.fx))),
+              __int_as_float(group_bcast<LPS, T>(__float_as_int(g.fy)))};
+}
+
+// Tap reuse across consecutive planes. A pixel's depth planes project to nearby points on the
+// epipolar line, so consecutive planes mostly share bilinear taps (unique taps per pixel-view,
+// synthetic DTU rig: 129 / 48 / 14 of 192 / 128 / 32 tap loads in stages 1 / 2 / 3). The 4
+// taps of a plane always occupy the 4 (x parity, y parity) classes, so tap (X, Y) is cached in
+// register slot (X&1, Y&1) with its position as tag: a plane loads only the slots whose tag
+// changed. The address unit's cost scales with the lanes that make a memory request (measured,
+// scripts/micro/ta_mask.hip: exec-masked and out-of-range lanes are equally free), so skipped
+// loads are skipped work.
+struct Slots {
+  floatx4_t v[4];
+  unsigned pos[4];
+};
+
+__device__ __forceinline__ void slots_reset(Slots& S) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) S.pos[s] = 0xFFFFFFFFu;  // no position packs to this
+}
+
+// The parity-slot rule: sample g's tap in slot sl = (x parity) | (y parity) << 1, and the
+// grid_sample weight (y weight) * (x weight), nw = (1-fy)(1-fx) ..., of g's tap at (X, Y) given
+// ea = 1 - fx and s = 1 - fy
+struct SlotTap {
+  int X, Y;
+};
+__device__ __forceinline__ SlotTap slot_tap(const Geom& g, int sl) {
+  return SlotTap{g.x0 + ((g.x0 ^ sl) & 1), g.y0 + ((g.y0 ^ (sl >> 1)) & 1)};
+}
+__device__ __forceinline__ float tap_weight(const Geom& g, float ea, float s, int X, int Y) {
+  return ((Y == g.y0) ? s : g.fy) * ((X == g.x0) ? ea : g.fx);
+}
+
+template <int C>
+__device__ __forceinline__ void fetch_reuse(const __amdgpu_buffer_rsrc_t rsrc, unsigned vbase, unsigned rowb, int W,
+                                            int H, const Geom& g, Slots& S, floatx4_t (&val)[4], float (&w)[4]) {
+  constexpr unsigned CB = C * 4;
+  const float ea = 1.f - g.fx, s = 1.f - g.fy;
+#pragma unroll
+  for (int sl = 0; sl < 4; ++sl) {
+    const SlotTap t = slot_tap(g, sl);
+    const unsigned key = (unsigned)(t.X + 2) | ((unsigned)(t.Y + 2) << 16);  // X, Y in [-2, 32767]
+    // branch-free: a lane whose slot still holds the tap issues the load with an out-of-range
+    // offset (no memory request; costs the address unit what an exec-masked lane costs, measured)
+    const bool need = key != S.pos[sl];
+    S.pos[sl] = key;
+    const bool inside = (unsigned)t.X < (unsigned)W && (unsigned)t.Y < (unsigned)H;  // outside: reads 0
+    const unsigned off = (need && inside) ? vbase + (unsigned)t.Y * rowb + (unsigned)t.X * CB : kOffOut;
+    const floatx4_t ld = buf_load_f32x4(rsrc, off);
+    S.v[sl] = need ? ld : S.v[sl];
+    val[sl] = S.v[sl];
+    w[sl] = tap_weight(g, ea, s, t.X, t.Y);
+  }
+}
+
+// Without the cache (stage 1: uniform planes ~1.4 px apart share few taps): the 4 taps in
+// grid_sample's order nw, ne, sw, se, so the interpolation's fma chain is the reference's.
+template <int C>
+__device__ __forceinline__ void fetch_full(const __amdgpu_buffer_rsrc_t rsrc, unsigned vbase, unsigned rowb, int W,
+                                           int H, const Geom& g, floatx4_t (&val)[4], float (&w)[4]) {
+  constexpr unsigned CB = C * 4;
+  const float we = g.fx, n = g.fy;
+  const float ea = 1.f - we, s = 1.f - n;
+  w[0] = s * ea;
+  w[1] = s * we;
+  w[2] = n * ea;
+  w[3] = n * we;
+  const unsigned xa = (unsigned)g.x0 < (unsigned)W ? (unsigned)g.x0 * CB : kAxisOut;
+  const unsigned xb = (unsigned)(g.x0 + 1) < (unsigned)W ? (unsigned)(g.x0 + 1) * CB : kAxisOut;
+  const unsigned yrow = vbase + (unsigned)g.y0 * rowb;
+  const unsigned ya = (unsigned)g.y0 < (unsigned)H ? yrow : kAxisOut;
+  const unsigned yb = (unsigned)(g.y0 + 1) < (unsigned)H ? yrow + rowb : kAxisOut;
+  val[0] = buf_load_f32x4(rsrc, ya + xa);
+  val[1] = buf_load_f32x4(rsrc, ya + xb);
+  val[2] = buf_load_f32x4(rsrc, yb + xa);
+  val[3] = buf_load_f32x4(rsrc, yb + xb);
+}
+
+// bilinear value of each channel (fixed slot order), times ref, summed in channel order
+__device__ __forceinline__ float combine(const floatx4_t (&v)[4], const float (&w)[4], const float4& r4) {
+  float acc = 0.f;
+  acc = acc + fmaf(v[3][0], w[3], fmaf(v[2][0], w[2], fmaf(v[1][0], w[1], v[0][0] * w[0]))) * r4.x;
+  acc = acc + fmaf(v[3][1], w[3], fmaf(v[2][1], w[2], fmaf(v[1][1], w[1], v[0][1] * w[0]))) * r4.y;
+  acc = acc + fmaf(v[3][2], w[3], fmaf(v[2][2], w[2], fmaf(v[1][2], w[1], v[0][2] * w[0]))) * r4.z;
+  acc = acc + fmaf(v[3][3], w[3], fmaf(v[2][3], w[2], fmaf(v[1][3], w[1], v[0][3] * w[0]))) * r4.w;
+  return acc;
+}
+
+// Rounds R0..R0+N-1: in round t the whole group samples plane slot t (geometry broadcast from
+// lane t), so each load instruction covers one contiguous C*4-byte row per group. Every
+// round's (masked) loads are issued before any is consumed.
+template <int C, bool REUSE, int R0, int N>
+__device__ __forceinline__ void rounds(const __amdgpu_buffer_rsrc_t rsrc, unsigned vbase, unsigned rowb, int W,
+                                       int H, const Geom& own, const float4& r4, Slots& S, float* part) {
+  floatx4_t v[N][4];
+  float w[N][4];
+#define TMVS_FETCH(I)                                                                          \
+  if constexpr (REUSE)                                                                         \
+    fetch_reuse<C>(rsrc, vbase, rowb, W, H, geom_bcast<C / 4, R0 + I>(own), S, v[I], w[I]); \
+  else                                                                                         \
+    fetch_full<C>(rsrc, vbase, rowb, W, H, geom_bcast<C / 4, R0 + I>(own), v[I], w[I]);
+  TMVS_FETCH(0)
+  if constexpr (N > 1) { TMVS_FETCH(1) }
+  if constexpr (N > 2) { TMVS_FETCH(2) }
+  if constexpr (N > 3) { TMVS_FETCH(3) }
+#undef TMVS_FETCH
+#pragma unroll
+  for (int i = 0; i < N; ++i) part[R0 + i] = combine(v[i], w[i], r4);
+}
+
+// Full channel sum of this lane's own plane (slot k): LPS rounds, then the reduce-scatter.
+template <int C, bool REUSE>
+__device__ __forceinline__ float plane_corr(const __amdgpu_buffer_rsrc_t rsrc, unsigned vbase, unsigned rowb, int W,
+                                            int H, const Geom& own, const float4& r4, int k, Slots& S) {
+  constexpr int LPS = C / 4;
+  // given weights at C = 8 / 16 run warp_pair_kernel, so the tap cache has one user
+  static_assert(!REUSE || C == 32, "the tap cache serves C = 32 only");
+  float p[LPS];
+  if constexpr (REUSE) {
+    // batches of 2 rounds: the cached slots plus a batch's loads fit the VGPR budget
+    rounds<C, true, 0, 2>(rsrc, vbase, rowb, W, H, own, r4, S, p);
+    __builtin_amdgcn_sched_barrier(0);
+    rounds<C, true, 2, 2>(rsrc, vbase, rowb, W, H, own, r4, S, p);
+    __builtin_amdgcn_sched_barrier(0);
+    rounds<C, true, 4, 2>(rsrc, vbase, rowb, W, H, own, r4, S, p);
+    __builtin_amdgcn_sched_barrier(0);
+    rounds<C, true, 6, 2>(rsrc, vbase, rowb, W, H, own, r4, S, p);
+  } else if constexpr (LPS <= 4) {
+    rounds<C, false, 0, LPS>(rsrc, vbase, rowb, W, H, own, r4, S, p);
+  } else {
+    rounds<C, false, 0, 4>(rsrc, vbase, rowb, W, H, own, r4, S, p);
+    rounds<C, false, 4, 4>(rsrc, vbase, rowb, W, H, own, r4, S, p);
+  }
+  return reduce_scatter<LPS>(p, k);
+}
+
+// The forward kernels serve a block's pixels from an XCD-contiguous tile; a lane past the image
+// works on the last pixel and stores nothing.
+struct Pixel {
+  int p, x, y;
+  bool active;
+};
+__device__ __forceinline__ Pixel clamp_pixel(int p, int HW, int W) {
+  const bool active = p < HW;
+  if (!active) p = HW - 1;
+  const int y = p / W;
+  return Pixel{p, p - y * W, y, active};
+}
+
+// Views outer (a view's consecutive planes hit the same source lines: L1 reuse), planes inner
+// and not unrolled: the plane's depth and running weighted sum live in this thread's LDS
+// column, so the rounds' independent loads are the only large live set.
+template <int C, int D, bool PW, bool PARTIAL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void warp_corr_kernel(
+    const float* __restrict__ ref, const float* __restrict__ src, const float* __restrict__ hyp,
+    const float* __restrict__ vw_in, float* __restrict__ sim_out, float* __restrict__ wsum_out,
+    float* __restrict__ vw_out, int V, int H, int W, int vw_shift, int vw_offset, WarpArgs args) {
+  constexpr int LPS = C / 4;          // lanes per pixel
+  constexpr int SPW = 64 / LPS;       // pixels per wave
+  constexpr int PIX = 4 * SPW;        // pixels per block
+  constexpr int DPT = D / LPS;        // depth planes owned per lane
+  static_assert(D % LPS == 0, "D must be a multiple of C/4");
+  // PixelwiseNet parameters in LDS (uniform-address reads broadcast); as kernel arguments
+  // they would occupy ~200 SGPRs and spill
+  __shared__ __attribute__((aligned(16))) float pw_lds[PW ? TMVS_PW_NPARAMS + 3 : 4];
+  __shared__ float dep_lds[DPT][256];
+  __shared__ float acc_lds[DPT][256];
+  __shared__ float sim_lds[PW ? DPT : 1][PW ? 256 : 1];
+  const int tid = threadIdx.x;
+  if constexpr (PW) {
+    if (tid < TMVS_PW_NPARAMS) pw_lds[tid] = args.pw[tid];
+  }
+  const int HW = H * W;
+  const int nblk = (HW + PIX - 1) / PIX;
+  const int tile = xcd_remap(blockIdx.x, nblk);
+  const int lane = tid & 63;
+  const int k = lane % LPS;
+  const Pixel px = clamp_pixel(tile * PIX + (tid >> 6) * SPW + lane / LPS, HW, W);
+  const int p = px.p;
+  const float fxp = (float)px.x, fyp = (float)px.y;
+  const float4 r4 = *reinterpret_cast<const float4*>(ref + (size_t)p * C + 4 * k);
+#pragma unroll
+  for (int j = 0; j < DPT; ++j) {
+    dep_lds[j][tid] = hyp[(size_t)(j * LPS + k) * HW + p];
+    acc_lds[j][tid] = 0.f;
+  }
+  if constexpr (PW) __syncthreads();  // pw_lds is shared; the columns are per thread
+  const float halfw = (float)(W - 1) / 2.f;
+  const float halfh = (float)(H - 1) / 2.f;
+  float wsum = PARTIAL ? 0.f : 1e-5f;
+  const __amdgpu_buffer_rsrc_t rsrc = raw_rsrc(src, V * HW * C * 4);
+  const unsigned rowb = (unsigned)W * C * 4;
+  const int Ws = W >> vw_shift, Hs = H >> vw_shift;
+
+  for (int v = 0; v < V; ++v) {
+    const float* R = args.proj[v];
+    Ray ray;
+    pixel_ray(R, fxp, fyp, args.rot_plain, ray);
+    const unsigned vbase = (unsigned)(v * HW * C * 4 + 16 * k);
+    float w = 0.f;
+    if constexpr (!PW) w = vw_in[(size_t)(vw_offset + v) * Hs * Ws + (px.y >> vw_shift) * Ws + (px.x >> vw_shift)];
+    float wm = 0.f;  // PW: running max of sigmoid (> 0, so 0 is neutral)
+    Slots S;  // tap cache, valid within one view: planes j*LPS + t run in depth order
+    slots_reset(S);
+#pragma unroll 1
+    for (int j = 0; j < DPT; ++j) {
+      const Geom own = project(ray, R[3], R[7], R[11], dep_lds[j][tid], halfw, halfh);
+      const float sim = plane_corr<C, !PW>(rsrc, vbase, rowb, W, H, own, r4, k, S) * (1.f / (float)C);  // C = 2^n: == / C
+      if constexpr (PW) {
+        sim_lds[j][tid] = sim;
+        int salt = 0;  // opaque offset: keeps the parameter reads from being hoisted into VGPRs
+        asm volatile("" : "+v"(salt));
+        const float lg = pixelwise_logit(sim, pw_lds + salt);
+        wm = fmaxf(wm, 1.f / (1.f + expf(-lg)));
+      } else {
+        acc_lds[j][tid] = acc_lds[j][tid] + sim * w;
+      }
+    }
+    if constexpr (PW) {
+      w = group_max<LPS>(wm);
+      if (px.active && k == 0) vw_out[(size_t)(vw_offset + v) * HW + p] = w;
+#pragma unroll 4
+      for (int j = 0; j < DPT; ++j) acc_lds[j][tid] = acc_lds[j][tid] + sim_lds[j][tid] * w;
+    }
+    wsum = wsum + w;
+  }
+  if (!px.active) return;
+#pragma unroll 4
+  for (int j = 0; j < DPT; ++j) {
+    const size_t o = (size_t)(j * LPS + k) * HW + p;
+    sim_out[o] = PARTIAL ? acc_lds[j][tid] : acc_lds[j][tid] / wsum;
+  }
+  if (PARTIAL && k == 0) wsum_out[p] = wsum;
+}
+
+__global__ void aggregate_finalize_kernel(float* __restrict__ sim, const float* __restrict__ wsum, int D, int HW) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= HW) return;
+  const float ws = 1e-5f + wsum[(size_t)blockIdx.y * HW + p];
+  float* s = sim + (size_t)blockIdx.y * D * HW + p;
+  for (int d = 0; d < D; ++d) s[(size_t)d * HW] = s[(size_t)d * HW] / ws;
+}
+
+// Materialising homo_warping for the reference seam: out [C][D][H][W] from NCHW src.
+__global__ void homo_warping_kernel(const float* __restrict__ src, const float* __restrict__ hyp,
+                                    float* __restrict__ out, int C, int D, int H, int W, WarpArgs args) {
+  const int HW = H * W;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= D * HW) return;
+  const int d = idx / HW, p = idx - d * HW;
+  const int py = p / W, px = p - py * W;
+  const float* R = args.proj[0];
+  Ray ray;
+  pixel_ray(R, (float)px, (float)py, args.rot_plain, ray);
+  const float dep = hyp[idx];
+  const float X = ray.x * dep + R[3], Y = ray.y * dep + R[7], Z = ray.z * dep + R[11];
+  const float halfw = (float)(W - 1) / 2.f, halfh = (float)(H - 1) / 2.f;
+  float xn = (X / Z) / halfw - 1.f, yn = (Y / Z) / halfh - 1.f;
+  if (Z < 1e-6f) {
+    xn = -99.f;
+    yn = -99.f;
+  }
+  const float ix = (xn + 1.f) * halfw, iy = (yn + 1.f) * halfh;
+  // project()'s arithmetic written out: through the helper the kernel measured 171.9 against 170.1 us
+  // (profiles/warp_scaffold_ab.txt), and its taps are tested in float, not on project()'s clamped integers,
+  // because this entry point puts no bound on W and H
+  const float x0 = floorf(ix), y0 = floorf(iy);
+  const float we = ix - x0, ea = 1.f - we, n = iy - y0, s = 1.f - n;
+  const float wnw = s * ea, wne = s * we, wsw = n * ea, wse = n * we;
+  const bool vx0 = x0 >= 0.f && x0 <= (float)(W - 1), vx1 = x0 + 1.f >= 0.f && x0 + 1.f <= (float)(W - 1);
+  const bool vy0 = y0 >= 0.f && y0 <= (float)(H - 1), vy1 = y0 + 1.f >= 0.f && y0 + 1.f <= (float)(H - 1);
+  const int xi0 = vx0 ? (int)x0 : 0, xi1 = vx1 ? (int)x0 + 1 : 0;
+  const int yi0 = vy0 ? (int)y0 : 0, yi1 = vy1 ? (int)y0 + 1 : 0;
+  for (int c = 0; c < C; ++c) {
+    const float* sc = src + (size_t)c * HW;
+    const float a = (vy0 && vx0) ? sc[yi0 * W + xi0] : 0.f;
+    const float b = (vy0 && vx1) ? sc[yi0 * W + xi1] : 0.f;
+    const float cc = (vy1 && vx0) ? sc[yi1 * W + xi0] : 0.f;
+    const float dd = (vy1 && vx1) ? sc[yi1 * W + xi1] : 0.f;
+    out[(size_t)c * D * HW + idx] = fmaf(dd, wse, fmaf(cc, wsw, fmaf(b, wne, a * wnw)));
+  }
+}
+
+// geometry of plane slot t (compile-time after unrolling) broadcast from lane t of the group
+template <int LPS>
+__device__ __forceinline__ Geom geom_round(const Geom& own, int t) {
+  if (t == 0) return geom_bcast<LPS, 0>(own);
+  if (t == 1) return geom_bcast<LPS, 1>(own);
+  if constexpr (LPS > 2) {
+    if (t == 2) return geom_bcast<LPS, 2>(own);
+    if (t == 3) return geom_bcast<LPS, 3>(own);
+  }
+  if constexpr (LPS > 4) {
+    if (t == 4) return geom_bcast<LPS, 4>(own);
+    if (t == 5) return geom_bcast<LPS, 5>(own);
+    if (t == 6) return geom_bcast<LPS, 6>(own);
+    return geom_bcast<LPS, 7>(own);
+  }
+  return own;
+}
+
+// Row-pair rounds R0..R0+N-1 (see warp_pair_kernel): in round t the group samples plane t;
+// this lane loads its tap column's two rows (one 16-byte channel quad each); all loads of the
+// batch are issued before any is consumed.
+template <int C, int R0, int N>
+__device__ __forceinline__ void pair_rounds(const __amdgpu_buffer_rsrc_t rsrc, unsigned vbase, unsigned rowb, int W,
+                                            int H, const Geom& own, const float4* r4, int tx, float* part) {
+  constexpr int LPS = C / 2;
+  floatx4_t top[N], bot[N];
+  float wt[N], wb[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const Geom g = geom_round<LPS>(own, R0 + i);
+    const int X = g.x0 + tx;
+    const unsigned ox = (unsigned)X < (unsigned)W ? (unsigned)X * (unsigned)(C * 4) : kAxisOut;
+    const unsigned yrow = vbase + (unsigned)g.y0 * rowb;
+    const unsigned oa = (unsigned)g.y0 < (unsigned)H ? yrow : kAxisOut;
+    const unsigned ob = (unsigned)(g.y0 + 1) < (unsigned)H ? yrow + rowb : kAxisOut;
+    top[i] = buf_load_f32x4(rsrc, oa + ox);
+    bot[i] = buf_load_f32x4(rsrc, ob + ox);
+    const float wx = tx ? g.fx : 1.f - g.fx;
+    wt[i] = (1.f - g.fy) * wx;  // grid_sample: (y weight) * (x weight)
+    wb[i] = g.fy * wx;
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const float4 r = r4[R0 + i];
+    float acc = 0.f;
+    acc = acc + fmaf(bot[i][0], wb[i], top[i][0] * wt[i]) * r.x;
+    acc = acc + fmaf(bot[i][1], wb[i], top[i][1] * wt[i]) * r.y;
+    acc = acc + fmaf(bot[i][2], wb[i], top[i][2] * wt[i]) * r.z;
+    acc = acc + fmaf(bot[i][3], wb[i], top[i][3] * wt[i]) * r.w;
+    part[R0 + i] = acc;
+  }
+}
+
+// Given view weights at C = 8 / 16 (stages 3 / 2): "row pair" lane layout. A pixel is served
+// by 2·C/4 lanes k = (tx, q): tx picks the tap column (x0 or x0+1), q the channel quad; in a
+// round the group's lanes load one contiguous 2·C·4-byte span per tap row (x0 and x0+1, all
+// channels; C = 8: 4 lanes, 64 bytes) instead of two lanes loading 32-byte rows of different
+// taps, so every lane quad of a load instruction stays on one span (measured with the C/4
+// layout: 48 address-unit cycles per instruction, stalled on the L1). Bilinear partial per
+// lane: its column's two taps; the reduce-scatter over the group then adds the columns and
+// the channel quads.
 template <int C, int D, bool PARTIAL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void warp_pair_kernel(
     const float* __restrict__ ref, const float* __restrict__ src, const float* __restrict__ hyp,
@@ -560,6 +552,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   constexpr int NQ = C / 4;             // channel quads
   constexpr int LPS = 2 * NQ;           // lanes per pixel: (tap column, quad)
   constexpr int SPW = 64 / LPS, PIX = 4 * SPW, DPT = D / LPS;
+  // Which samples share a load instruction. Plane-major rounds (the original layout): in round t the
+  // wave's SPW groups sample SPW pixels at one plane each. Pixel-major rounds (used for C = 16): the
+  // SPW groups sample PPR = SPW/LPS pixels × LPS consecutive planes each (stage 2:
+  // 1 pixel × 8 planes), whose taps lie ≈0.7 px apart on one epipolar segment and so share cache lines.
+  // Group g's round-t sample is owned by its lane t (geometry broadcast as before), so lane (g, k) owns
+  // pixel k·PPR + g/LPS at planes j·LPS + g%LPS and holds the reference quads of the LPS pixels its
+  // rounds visit. Each sample's arithmetic (lane roles, channel order, reduce-scatter) is unchanged:
+  // the outputs are bit-identical either way. Measured (profiles/r13/warp_pmajor_ab.txt, two
+  // alternating reps in one box): stage 2 345.1 -> 323.3 us, stage 3 247.2 -> 252.1 us (the address
+  // unit is charged per 4-lane quad, so sharing lines between quads buys little); C = 8 keeps the
+  // plane-major rounds.
   constexpr bool PM = C == 16;               // pixel-major rounds
   constexpr int PPR = PM ? SPW / LPS : SPW;  // pixels per round
   static_assert(C == 8 || C == 16, "row-pair layout for 8 or 16 channels");
@@ -577,11 +580,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // owned samples: pixel `p`, planes j·LPS + dsub (pixel-major) or j·LPS + k (plane-major)
   const int pix_own = PM ? k * PPR + g / LPS : g;
   const int dsub = PM ? g % LPS : k;
-  int p = wbase + pix_own;
-  const bool active = p < HW;
-  if (!active) p = HW - 1;
-  const int py = p / W, px = p - py * W;
-  const float fxp = (float)px, fyp = (float)py;
+  const Pixel px = clamp_pixel(wbase + pix_own, HW, W);
+  const int p = px.p;
+  const float fxp = (float)px.x, fyp = (float)px.y;
   float4 r4[LPS];  // reference quad q of the pixel round t samples
 #pragma unroll
   for (int t = 0; t < LPS; ++t) {
@@ -596,22 +597,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const float halfw = (float)(W - 1) / 2.f;
   const float halfh = (float)(H - 1) / 2.f;
   const int Ws = W >> vw_shift, Hs = H >> vw_shift;
-  const float* wv = vw_in + (size_t)vw_offset * Hs * Ws + (py >> vw_shift) * Ws + (px >> vw_shift);
+  const float* wv = vw_in + (size_t)vw_offset * Hs * Ws + (px.y >> vw_shift) * Ws + (px.x >> vw_shift);
   float wsum = PARTIAL ? 0.f : 1e-5f;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)src, (short)0, V * HW * C * 4, kRsrcWord3);
+  const __amdgpu_buffer_rsrc_t rsrc = raw_rsrc(src, V * HW * C * 4);
   const unsigned rowb = (unsigned)W * C * 4;
   for (int v = 0; v < V; ++v) {
     const float* R = args.proj[v];
-    const float rx = rot_row(R, fxp, fyp, args.rot_plain);
-    const float ry = rot_row(R + 4, fxp, fyp, args.rot_plain);
-    const float rz = rot_row(R + 8, fxp, fyp, args.rot_plain);
+    Ray ray;
+    pixel_ray(R, fxp, fyp, args.rot_plain, ray);
     const unsigned vbase = (unsigned)(v * HW * C * 4 + 16 * q);
     const float w = wv[(size_t)v * Hs * Ws];
 #pragma unroll 1
     for (int j = 0; j < DPT; ++j) {
-      Geom own;
-      project(rx, ry, rz, R[3], R[7], R[11], dep_lds[j][tid], halfw, halfh, own.x0, own.y0, own.fx, own.fy);
+      const Geom own = project(ray, R[3], R[7], R[11], dep_lds[j][tid], halfw, halfh);
       float part[LPS];
       pair_rounds<C, 0, (LPS < 4 ? LPS : 4)>(rsrc, vbase, rowb, W, H, own, r4, tx, part);
       if constexpr (LPS == 8) {
@@ -623,7 +621,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
     wsum = wsum + w;
   }
-  if (!active) return;
+  if (!px.active) return;
 #pragma unroll 4
   for (int j = 0; j < DPT; ++j) {
     const size_t o = (size_t)(j * LPS + dsub) * HW + p;
@@ -632,61 +630,54 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   if (PARTIAL && dsub == 0) wsum_out[p] = wsum;
 }
 
+// One sample's launch: built once by the entry point, so each dispatch level names only what it switches on
+struct WarpLaunch {
+  const float *ref, *src, *hyp, *vw_in;
+  float *sim, *wsum, *vw_out;
+  int V, H, W, vw_shift, vw_offset;
+  WarpArgs args;
+  hipStream_t st;
+};
+
+// given weights at C = 8 / 16 take the row-pair kernel, everything else the C/4 layout
 template <int C, int D, bool PW, bool PARTIAL>
-static int launch_warp(const float* ref, const float* src, const float* hyp, const float* vw_in, float* sim,
-                       float* wsum, float* vw_out, int V, int H, int W, int vw_shift, int vw_offset, int vw_total,
-                       const WarpArgs& args, hipStream_t st) {
-  if constexpr ((C == 8 || C == 16) && !PW) {
-    constexpr int PIXP = 4 * (64 / (C / 2));
-    const int nblk = (H * W + PIXP - 1) / PIXP;
-    hipLaunchKernelGGL((warp_pair_kernel<C, D, PARTIAL>), dim3(nblk), dim3(256), 0, st, ref, src, hyp, vw_in, sim,
-                       wsum, V, H, W, vw_shift, vw_offset, args);
-    TMVS_CHECK_LAUNCH();
-    return TMVS_OK;
-  }
-  constexpr int PIX = 4 * (64 / (C / 4));
-  const int nblk = (H * W + PIX - 1) / PIX;
-  hipLaunchKernelGGL((warp_corr_kernel<C, D, PW, PARTIAL>), dim3(nblk), dim3(256), 0, st, ref, src, hyp, vw_in, sim,
-                     wsum, vw_out, V, H, W, vw_shift, vw_offset, vw_total, args);
+static int launch_warp(const WarpLaunch& L) {
+  constexpr bool PAIR = (C == 8 || C == 16) && !PW;
+  constexpr int PIX = 4 * (64 / (PAIR ? C / 2 : C / 4));
+  const dim3 grid((L.H * L.W + PIX - 1) / PIX);
+  if constexpr (PAIR)
+    hipLaunchKernelGGL((warp_pair_kernel<C, D, PARTIAL>), grid, dim3(256), 0, L.st, L.ref, L.src, L.hyp, L.vw_in, L.sim,
+                       L.wsum, L.V, L.H, L.W, L.vw_shift, L.vw_offset, L.args);
+  else
+    hipLaunchKernelGGL((warp_corr_kernel<C, D, PW, PARTIAL>), grid, dim3(256), 0, L.st, L.ref, L.src, L.hyp, L.vw_in,
+                       L.sim, L.wsum, L.vw_out, L.V, L.H, L.W, L.vw_shift, L.vw_offset, L.args);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }
 
-template <int C, bool PW, bool PARTIAL>
-static int dispatch_depth(int D, const float* ref, const float* src, const float* hyp, const float* vw_in, float* sim,
-                          float* wsum, float* vw_out, int V, int H, int W, int vw_shift, int vw_offset, int vw_total,
-                          const WarpArgs& a, hipStream_t st) {
-#define TMVS_WARP_CASE(DD)                                                                                        \
-  if (D == DD)                                                                                                    \
-    return launch_warp<C, DD, PW, PARTIAL>(ref, src, hyp, vw_in, sim, wsum, vw_out, V, H, W, vw_shift, vw_offset, \
-                                           vw_total, a, st);
-  TMVS_WARP_CASE(48)
-  TMVS_WARP_CASE(32)
-  TMVS_WARP_CASE(16)
-  TMVS_WARP_CASE(8)
-  TMVS_WARP_CASE(64)
-  TMVS_WARP_CASE(24)
-#undef TMVS_WARP_CASE
-  return TMVS_ERR_SHAPE;
+// f(std::integral_constant<int, v>) for the listed v equal to x, tried in list order; no such v: a shape error
+template <int... Vs, class F>
+static int dispatch_int(int x, std::integer_sequence<int, Vs...>, F&& f) {
+  int rc = TMVS_ERR_SHAPE;
+  (void)((x == Vs && (rc = f(std::integral_constant<int, Vs>{}), true)) || ...);
+  return rc;
+}
+using WarpChannels = std::integer_sequence<int, 8, 16, 32>;
+using WarpDepths = std::integer_sequence<int, 48, 32, 16, 8, 64, 24>;
+
+template <int C, int D>
+static int dispatch_mode(bool pw, bool partial, const WarpLaunch& L) {
+  if (pw) return partial ? launch_warp<C, D, true, true>(L) : launch_warp<C, D, true, false>(L);
+  return partial ? launch_warp<C, D, false, true>(L) : launch_warp<C, D, false, false>(L);
 }
 
-template <int C>
-static int dispatch_mode(bool pw, bool partial, int D, const float* ref, const float* src, const float* hyp,
-                         const float* vw_in, float* sim, float* wsum, float* vw_out, int V, int H, int W, int vw_shift,
-                         int vw_offset, int vw_total, const WarpArgs& a, hipStream_t st) {
-  if (pw && partial)
-    return dispatch_depth<C, true, true>(D, ref, src, hyp, vw_in, sim, wsum, vw_out, V, H, W, vw_shift, vw_offset,
-                                         vw_total, a, st);
-  if (pw)
-    return dispatch_depth<C, true, false>(D, ref, src, hyp, vw_in, sim, wsum, vw_out, V, H, W, vw_shift, vw_offset,
-                                          vw_total, a, st);
-  if (partial)
-    return dispatch_depth<C, false, true>(D, ref, src, hyp, vw_in, sim, wsum, vw_out, V, H, W, vw_shift, vw_offset,
-                                          vw_total, a, st);
-  return dispatch_depth<C, false, false>(D, ref, src, hyp, vw_in, sim, wsum, vw_out, V, H, W, vw_shift, vw_offset,
-                                         vw_total, a, st);
+static int dispatch_warp(int channels, int ndepth, bool pw, bool partial, const WarpLaunch& L) {
+  return dispatch_int(channels, WarpChannels{}, [&](auto c) {
+    return dispatch_int(ndepth, WarpDepths{}, [&](auto d) {
+      return dispatch_mode<decltype(c)::value, decltype(d)::value>(pw, partial, L);
+    });
+  });
 }
-
 
 // ---------------------------------------------------------------- backward (training, C5)
 // Adjoint of the per-view similarity sim_v[d][p] = (1/C) sum_c ref[p][c] * bilinear(src_v, X(v,d,p))[c]
@@ -812,20 +803,18 @@ __global__ __launch_bounds__(256) void warp_corr_bwd_kernel(const float* __restr
   };
   {
     const float* R = args.proj[v];
-    const float rx = rot_row(R, fxp, fyp, args.rot_plain);
-    const float ry = rot_row(R + 4, fxp, fyp, args.rot_plain);
-    const float rz = rot_row(R + 8, fxp, fyp, args.rot_plain);
+    Ray ray;
+    pixel_ray(R, fxp, fyp, args.rot_plain, ray);
     const float* sv = src + (size_t)v * HW * C;
 #pragma unroll 1
     for (int d = d0; d < d1; ++d) {
       const float g = live ? dsim[((size_t)v * D + d) * HW + pc] * (1.f / (float)C) : 0.f;  // C = 2^n: exact
-      int x0, y0;
-      float fx, fy;
-      project(rx, ry, rz, R[3], R[7], R[11], hyp[(size_t)d * HW + pc], halfw, halfh, x0, y0, fx, fy);
-      const float ea = 1.f - fx, s = 1.f - fy;
+      const Geom gm = project(ray, R[3], R[7], R[11], hyp[(size_t)d * HW + pc], halfw, halfh);
+      const int x0 = gm.x0, y0 = gm.y0;
+      const float ea = 1.f - gm.fx, s = 1.f - gm.fy;
       const bool act = g != 0.f;
       if (act) {
-        const float wt[4] = {s * ea, s * fx, fy * ea, fy * fx};  // nw, ne, sw, se (grid_sample)
+        const float wt[4] = {s * ea, s * gm.fx, gm.fy * ea, gm.fy * gm.fx};  // nw, ne, sw, se (grid_sample)
         const int tx[4] = {x0, x0 + 1, x0, x0 + 1}, ty[4] = {y0, y0, y0 + 1, y0 + 1};
         bool in[4];
         const float* tp[4];
@@ -859,10 +848,10 @@ __global__ __launch_bounds__(256) void warp_corr_bwd_kernel(const float* __restr
       if constexpr (SCATTER)
 #pragma unroll
       for (int sl = 0; sl < 4; ++sl) {
-        const int X = x0 + ((x0 ^ sl) & 1), Y = y0 + ((y0 ^ (sl >> 1)) & 1);
-        const bool inside = (unsigned)X < (unsigned)W && (unsigned)Y < (unsigned)H;
-        const float wgt = ((Y == y0) ? s : fy) * ((X == x0) ? ea : fx);
-        const unsigned key = inside ? ((unsigned)Y << 16) | (unsigned)X : 0xFFFFFFFFu;
+        const SlotTap t = slot_tap(gm, sl);
+        const bool inside = (unsigned)t.X < (unsigned)W && (unsigned)t.Y < (unsigned)H;
+        const float wgt = tap_weight(gm, ea, s, t.X, t.Y);
+        const unsigned key = inside ? ((unsigned)t.Y << 16) | (unsigned)t.X : 0xFFFFFFFFu;
         const bool change = act && key != skey[sl];
         flush(sl, change);
         if (change) {
@@ -986,18 +975,14 @@ __global__ __launch_bounds__(256) void warp_bwd_src_planes_kernel(const float* _
       const float fyp = (float)py;
 #pragma unroll 1
       for (int px = bx0; px <= bx1; ++px) {
-        const float fxp = (float)px;
-        const float rx = rot_row(R, fxp, fyp, args.rot_plain);
-        const float ry = rot_row(R + 4, fxp, fyp, args.rot_plain);
-        const float rz = rot_row(R + 8, fxp, fyp, args.rot_plain);
-        int x0, y0;
-        float fx, fy;
-        project(rx, ry, rz, R[3], R[7], R[11], dep, halfw, halfh, x0, y0, fx, fy);
-        const int dx = qx - x0, dy = qy - y0;
+        Ray ray;
+        pixel_ray(R, (float)px, fyp, args.rot_plain, ray);
+        const Geom gm = project(ray, R[3], R[7], R[11], dep, halfw, halfh);
+        const int dx = qx - gm.x0, dy = qy - gm.y0;
         if ((unsigned)dx > 1u || (unsigned)dy > 1u) continue;
         const int p = py * W + px;
         const float g = gd[p] * (1.f / (float)C);  // C = 2^n: exact
-        const float wgt = (dy == 0 ? 1.f - fy : fy) * (dx == 0 ? 1.f - fx : fx);
+        const float wgt = (dy == 0 ? 1.f - gm.fy : gm.fy) * (dx == 0 ? 1.f - gm.fx : gm.fx);
         const float coef = wgt * g;
         const float* rp = ref + (size_t)p * C;
 #pragma unroll
@@ -1071,42 +1056,29 @@ extern "C" int tmvs_warp_corr(const float* ref_fea, const float* src_fea, const 
   // remainder would put the last column / row at index W >> vw_shift / H >> vw_shift, past the map
   if (!pw && (vw_shift > 14 || (height & ((1 << vw_shift) - 1)) || (width & ((1 << vw_shift) - 1))))
     return TMVS_ERR_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
   const size_t HW = (size_t)height * width;
+  const size_t hs = (size_t)(height >> vw_shift) * (width >> vw_shift);
   for (int b = 0; b < batch; ++b) {
-    WarpArgs a;
-    a.rot_plain = (flags & TMVS_WARP_ROT_PLAIN) ? 1 : 0;
+    WarpLaunch L = {};  // zeroes args.pw where PixelwiseNet does not run
+    L.ref = ref_fea + (size_t)b * HW * channels;
+    L.src = src_fea + (size_t)b * n_src * HW * channels;
+    L.hyp = hyp + (size_t)b * ndepth * HW;
+    L.vw_in = pw ? nullptr : view_w_in + (size_t)b * vw_total * hs;
+    L.sim = sim_out + (size_t)b * ndepth * HW;
+    L.wsum = partial ? wsum_out + (size_t)b * HW : nullptr;
+    L.vw_out = pw ? view_w_out + (size_t)b * vw_total * HW : nullptr;
+    L.V = n_src;
+    L.H = height;
+    L.W = width;
+    L.vw_shift = vw_shift;
+    L.vw_offset = vw_offset;
+    L.st = (hipStream_t)stream;
+    L.args.rot_plain = (flags & TMVS_WARP_ROT_PLAIN) ? 1 : 0;
     for (int v = 0; v < n_src; ++v)
-      for (int k = 0; k < 12; ++k) a.proj[v][k] = proj[((size_t)b * n_src + v) * 12 + k];
+      for (int k = 0; k < 12; ++k) L.args.proj[v][k] = proj[((size_t)b * n_src + v) * 12 + k];
     if (pw)
-      for (int k = 0; k < TMVS_PW_NPARAMS; ++k) a.pw[k] = pw_params[k];
-    else
-      for (int k = 0; k < TMVS_PW_NPARAMS; ++k) a.pw[k] = 0.f;
-    const float* rb = ref_fea + (size_t)b * HW * channels;
-    const float* sb = src_fea + (size_t)b * n_src * HW * channels;
-    const float* hb = hyp + (size_t)b * ndepth * HW;
-    const size_t hs = (size_t)(height >> vw_shift) * (width >> vw_shift);
-    const float* vib = pw ? nullptr : view_w_in + (size_t)b * vw_total * hs;
-    float* sob = sim_out + (size_t)b * ndepth * HW;
-    float* wob = partial ? wsum_out + (size_t)b * HW : nullptr;
-    float* vob = pw ? view_w_out + (size_t)b * vw_total * HW : nullptr;
-    int rc;
-    switch (channels) {
-      case 32:
-        rc = dispatch_mode<32>(pw, partial, ndepth, rb, sb, hb, vib, sob, wob, vob, n_src, height, width, vw_shift,
-                               vw_offset, vw_total, a, st);
-        break;
-      case 16:
-        rc = dispatch_mode<16>(pw, partial, ndepth, rb, sb, hb, vib, sob, wob, vob, n_src, height, width, vw_shift,
-                               vw_offset, vw_total, a, st);
-        break;
-      case 8:
-        rc = dispatch_mode<8>(pw, partial, ndepth, rb, sb, hb, vib, sob, wob, vob, n_src, height, width, vw_shift,
-                              vw_offset, vw_total, a, st);
-        break;
-      default:
-        return TMVS_ERR_SHAPE;
-    }
+      for (int k = 0; k < TMVS_PW_NPARAMS; ++k) L.args.pw[k] = pw_params[k];
+    const int rc = dispatch_warp(channels, ndepth, pw, partial, L);
     if (rc != TMVS_OK) return rc;
   }
   return TMVS_OK;
@@ -1184,26 +1156,20 @@ extern "C" int tmvs_warp_corr_backward(const float* ref_fea, const float* src_fe
   float* part = (float*)((char*)workspace + (size_t)n * sizeof(unsigned long long) + 256);
   const dim3 grid((HW + 255) / 256, n_src, nch);
   const dim3 pgrid((HW + 63) / 64, n_src);
-#define TMVS_BWD_CASE(CC)                                                                                              \
-  case CC:                                                                                                             \
-    if (planes) {                                                                                                      \
-      hipLaunchKernelGGL((warp_corr_bwd_kernel<CC, false>), grid, dim3(256), 0, st, ref_fea, src_fea, hyp, dsim, n_src, \
-                         ndepth, height, width, dchunk, a, part, fix, absmax);                                          \
-      hipLaunchKernelGGL(warp_bwd_src_planes_kernel<CC>, pgrid, dim3(256), 0, st, ref_fea, hyp, dsim, ndepth, height,   \
-                         width, a, dsrc, ovf);                                                                          \
-    } else {                                                                                                           \
-      hipLaunchKernelGGL((warp_corr_bwd_kernel<CC, true>), grid, dim3(256), 0, st, ref_fea, src_fea, hyp, dsim, n_src,  \
-                         ndepth, height, width, dchunk, a, part, fix, absmax);                                          \
-    }                                                                                                                  \
-    break;
-  switch (channels) {
-    TMVS_BWD_CASE(8)
-    TMVS_BWD_CASE(16)
-    TMVS_BWD_CASE(32)
-    default:
-      return TMVS_ERR_SHAPE;
-  }
-#undef TMVS_BWD_CASE
+  const int rc = dispatch_int(channels, WarpChannels{}, [&](auto c) {
+    constexpr int C = decltype(c)::value;
+    if (planes) {
+      hipLaunchKernelGGL((warp_corr_bwd_kernel<C, false>), grid, dim3(256), 0, st, ref_fea, src_fea, hyp, dsim, n_src,
+                         ndepth, height, width, dchunk, a, part, fix, absmax);
+      hipLaunchKernelGGL(warp_bwd_src_planes_kernel<C>, pgrid, dim3(256), 0, st, ref_fea, hyp, dsim, ndepth, height,
+                         width, a, dsrc, ovf);
+    } else {
+      hipLaunchKernelGGL((warp_corr_bwd_kernel<C, true>), grid, dim3(256), 0, st, ref_fea, src_fea, hyp, dsim, n_src,
+                         ndepth, height, width, dchunk, a, part, fix, absmax);
+    }
+    return TMVS_OK;
+  });
+  if (rc != TMVS_OK) return rc;
   TMVS_CHECK_LAUNCH();
   const long nref = (long)HW * channels;
   hipLaunchKernelGGL(sum_dref_parts_kernel, dim3((unsigned)((nref + 255) / 256)), dim3(256), 0, st, (const float*)part,
