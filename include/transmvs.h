@@ -607,6 +607,39 @@ size_t tmvs_depth_metrics_workspace(int n);
 int tmvs_depth_metrics(const float* depth, const float* depth_gt, const float* mask, int n, float depth_interval,
                        void* workspace, size_t workspace_bytes, float* out, void* stream);
 
+/* ------------------------------------------------------------------ training driver (transmvsnet_amd.finetune)
+ * tmvs_gt_pyramid: one training sample's ground truth -- depth and mask at the three stage sizes -- from the
+ * reference view's raw depth map in one launch; every cv2.resize(INTER_NEAREST) of the dataset classes is a
+ * gather through index tables the host composes (transmvsnet_amd.data.nearest_axis: source index
+ * min(floor(x * (1.0 / (dst / src))), src - 1) in double, no half-pixel offset).
+ *   mode TMVS_GT_BLD (datasets/bld_train.py:134-148): stage 3 [src_h][src_w] is the raw map, stages 2 / 1 are
+ *     [src_h/2][src_w/2] and [src_h/4][src_w/4]; mask = depth >= depth_min && depth <= depth_end in float32
+ *     (NaN: 0). mask_png, target_h and target_w are not read.
+ *   mode TMVS_GT_DTU (datasets/dtu_yao.py:75-122, prepare_img): nearest to (src_w/2, src_h/2), centre crop to
+ *     [target_h][target_w] starting at ((src_h/2 - target_h)/2, (src_w/2 - target_w)/2) = stage 3, then stages
+ *     2 / 1 at target/2 and target/4; mask = mask_png > 10, mask_png [src_h][src_w] uint8 the raw
+ *     depth_visual PNG sent through the same indices. depth_min / depth_end are not read.
+ *   rows [H3 + H2 + H1], cols [W3 + W2 + W1] (DEVICE int32, stage 3 first): the source row / column of every
+ *     output row / column, the whole chain composed; entries outside the source are clamped into it.
+ *   depth3..1, mask3..1: the six outputs, float32 (mask 1.0 / 0.0).
+ * Null pointer or unknown mode: TMVS_ERR_ARG. Non-positive size, a crop larger than the halved image, or an
+ * empty stage 1 (stage-3 side < 4): TMVS_ERR_SHAPE. Additions: no earlier signature or behaviour changes with
+ * them, so TMVS_ABI_VERSION stays as it was.                                                               */
+#define TMVS_GT_BLD 0
+#define TMVS_GT_DTU 1
+int tmvs_gt_pyramid(int mode, const float* depth, const unsigned char* mask_png, int src_h, int src_w, int target_h,
+                    int target_w, float depth_min, float depth_end, const int* rows, const int* cols, float* depth3,
+                    float* depth2, float* depth1, float* mask3, float* mask2, float* mask1, void* stream);
+/* The twelve DTU validation scalars of train.py:216-228 (utils.py:155-175) over the n elements with
+ * mask > 0.5, err = |depth_est - depth_gt| in float32. out (device, 12 floats): [0] abs_depth_error (mean),
+ * [1..5] the fraction with err > 2, 4, 8, 14, 20, [6..11] the mean err over the bins [0,2] [2,4] [4,8] [8,14]
+ * [14,20] [20,1e5], both ends inclusive, 0 for an empty bin. An empty mask gives NaN for [0..5], 0 for the
+ * bins. Counts are integers; sums are combined in a fixed order (bitwise repeatable). workspace:
+ * tmvs_depth_eval_metrics_workspace(n) bytes of 8-byte aligned device memory. n <= 0 is TMVS_ERR_ARG.     */
+size_t tmvs_depth_eval_metrics_workspace(int n);
+int tmvs_depth_eval_metrics(const float* depth_est, const float* depth_gt, const float* mask, int n, void* workspace,
+                            size_t workspace_bytes, float* out, void* stream);
+
 /* ------------------------------------------------------------------ FeatureNet training
  * The backward of FeatureNet (models/module.py:343-422) and of its DCNs (models/dcn.py:66-80 ->
  * torchvision.ops.deform_conv2d), and of the softmax of prob_volume (models/TransMVSNet.py:99).

@@ -67,6 +67,9 @@ SIGNATURES = {
     "tmvs_entropy_loss": (I, [P, P, I, P, P, I, I, I, I, F, P, S, P, P, P, P, P]),
     "tmvs_depth_metrics_workspace": (S, [I]),
     "tmvs_depth_metrics": (I, [P, P, P, I, F, P, S, P, P]),
+    "tmvs_gt_pyramid": (I, [I, P, P, I, I, I, I, F, F, P, P, P, P, P, P, P, P, P]),
+    "tmvs_depth_eval_metrics_workspace": (S, [I]),
+    "tmvs_depth_eval_metrics": (I, [P, P, P, I, P, S, P, P]),
     "tmvs_warp_corr_backward_workspace": (S, [I, I, I, I, I]),
     "tmvs_warp_corr_backward": (I, [P, P, P, P, P, I, I, I, I, I, I, P, S, P, P, P]),
     "tmvs_pixelwise_train_workspace": (S, []),
@@ -136,6 +139,7 @@ DYNFUSE_REF_FLOATS = 24
 DYNFUSE_MAX_SRC = 10
 DYNFUSE_PHOTO, DYNFUSE_GEO, DYNFUSE_FINAL = 1, 2, 4
 DTU_UNDECIDED, DTU_KEPT, DTU_REMOVED = 0, 1, 2
+GT_BLD, GT_DTU = 0, 1
 
 
 class CostRegWeights(ctypes.Structure):

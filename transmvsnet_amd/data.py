@@ -12,6 +12,10 @@ scans can be fed to ``TransMVSNet.forward`` instead of synthetic tensors.
   load_sample_tnt              datasets/tnt_eval.py:120-210 (cams_1/, per-scan image_sizes caps, nviews
                                shrunk to 1 + #sources, np.arange(dmin, dint*nd + dmin, dint), optional
                                inverse-depth hypotheses, the dataset-wide fixed resolution)
+  build_list_bld / read_cam_file_bld            datasets/bld_train.py:30-75 (the training set of finetune.py)
+  build_list_dtu_train / read_cam_file_dtu_train  datasets/dtu_yao.py:26-67 (7 lights per view, interval x 1.06)
+  nearest_axis / gt_pyramid_tables   cv2.resize(INTER_NEAREST)'s index rule and the tables tmvs_gt_pyramid
+                               gathers through (transmvsnet_amd.finetune holds the dataset classes)
 
 Host-side, as in the reference (its DataLoader workers). The reference resizes with
 cv2.resize(INTER_LINEAR) -- absent here; ``resize_bilinear`` restates OpenCV's float path
@@ -256,3 +260,105 @@ def load_sample(datapath, scan, ref_view, src_views, nviews=5, ndepths=192, inte
         if i == 0:
             depth_values = np.arange(dmin, dint * (ndepths - 0.5) + dmin, dint, dtype=np.float32)
     return _stack_sample(imgs, projs, depth_values, scan, view_ids[0])
+
+
+# ------------------------------------------------------------------ training sets (bld_train.py, dtu_yao.py)
+def nearest_axis(n_out, n_in):
+    """One axis of cv2.resize(..., INTER_NEAREST): per output index x the source index
+    min(floor(x * (1.0 / (n_out / n_in))), n_in - 1) in float64 (no half-pixel offset), int32."""
+    inv = 1.0 / (np.float64(n_out) / np.float64(n_in))
+    return np.minimum(np.floor(np.arange(n_out, dtype=np.float64) * inv), n_in - 1).astype(np.int32)
+
+
+def resize_nearest(img, new_w, new_h):
+    """cv2.resize(img, (new_w, new_h), interpolation=cv2.INTER_NEAREST) for an [h, w] map."""
+    h, w = img.shape[:2]
+    return img[nearest_axis(int(new_h), h)][:, nearest_axis(int(new_w), w)]
+
+
+def gt_pyramid_tables(h, w, mode="bld", target_hw=(512, 640)):
+    """The index tables of tmvs_gt_pyramid for an h x w raw map: (rows, cols, (H3, W3)), int32, the source row
+    / column of every output row / column of stage 3, then stage 2, then stage 1, with the whole chain composed.
+    mode "bld" (bld_train.py:139-148): stage 3 is the raw map, stages 2 / 1 nearest to (w//2, h//2) and
+    (w//4, h//4). mode "dtu" (dtu_yao.py:75-122): nearest to (w//2, h//2), centre crop to target_hw starting at
+    ((h//2 - th)//2, (w//2 - tw)//2), then stages 2 / 1 at the crop's //2 and //4."""
+    if mode == "bld":
+        base_r, base_c = np.arange(h, dtype=np.int32), np.arange(w, dtype=np.int32)
+    elif mode == "dtu":
+        th, tw = int(target_hw[0]), int(target_hw[1])
+        if th <= 0 or tw <= 0 or th > h // 2 or tw > w // 2:
+            raise ValueError(f"gt_pyramid_tables: the crop {th} x {tw} does not fit the halved image {h // 2} x {w // 2}")
+        sh, sw = (h // 2 - th) // 2, (w // 2 - tw) // 2
+        base_r = nearest_axis(h // 2, h)[sh:sh + th]
+        base_c = nearest_axis(w // 2, w)[sw:sw + tw]
+    else:
+        raise ValueError(f"gt_pyramid_tables: mode must be 'bld' or 'dtu', got {mode!r}")
+    h3, w3 = len(base_r), len(base_c)
+    if h3 < 4 or w3 < 4:
+        raise ValueError("gt_pyramid_tables: the stage-3 size must be at least 4 x 4")
+    rows = np.concatenate([base_r] + [base_r[nearest_axis(h3 // k, h3)] for k in (2, 4)]).astype(np.int32)
+    cols = np.concatenate([base_c] + [base_c[nearest_axis(w3 // k, w3)] for k in (2, 4)]).astype(np.int32)
+    return rows, cols, (h3, w3)
+
+
+def _cam_matrices(lines):
+    extrinsics = np.array(" ".join(lines[1:5]).split(), np.float32).reshape(4, 4)
+    intrinsics = np.array(" ".join(lines[7:10]).split(), np.float32).reshape(3, 3)
+    return intrinsics, extrinsics
+
+
+def read_cam_file_bld(filename, ndepths=192):
+    """bld_train.MVSDataset.read_cam_file (:58-75): intrinsics / 4; depth_interval = (max - min) / ndepths with
+    max the LAST field of line 11. Returns (intrinsics, extrinsics, depth_min, depth_interval)."""
+    with open(filename) as f:
+        lines = [ln.rstrip() for ln in f.readlines()]
+    intrinsics, extrinsics = _cam_matrices(lines)
+    intrinsics[:2, :] /= 4.0
+    depth_min = float(lines[11].split()[0])
+    depth_max = float(lines[11].split()[-1])
+    return intrinsics, extrinsics, depth_min, float(depth_max - depth_min) / ndepths
+
+
+def read_cam_file_dtu_train(filename, interval_scale=1.06):
+    """dtu_yao.MVSDataset.read_cam_file (:53-67): the intrinsics as stored (Cameras/train is already at the
+    feature scale), depth_interval = line 11's second field x interval_scale."""
+    with open(filename) as f:
+        lines = [ln.rstrip() for ln in f.readlines()]
+    intrinsics, extrinsics = _cam_matrices(lines)
+    depth_min = float(lines[11].split()[0])
+    return intrinsics, extrinsics, depth_min, float(lines[11].split()[1]) * interval_scale
+
+
+def _read_scans(listfile):
+    with open(listfile) as f:
+        return [line.rstrip() for line in f.readlines()]
+
+
+def _read_pairs(filename):
+    with open(filename) as f:
+        for _ in range(int(f.readline())):
+            ref = int(f.readline().rstrip())
+            yield ref, [int(x) for x in f.readline().rstrip().split()[1::2]]
+
+
+def build_list_bld(datapath, listfile, nviews):
+    """bld_train.MVSDataset.build_list (:30-53): [(scan, ref_view, src_views)]; a reference view with fewer
+    than nviews - 1 sources is skipped."""
+    metas = []
+    for scan in _read_scans(listfile):
+        for ref, src in _read_pairs(os.path.join(datapath, "{}/cams/pair.txt".format(scan))):
+            if len(src) < nviews - 1:
+                continue
+            metas.append((scan, ref, src))
+    return metas
+
+
+def build_list_dtu_train(datapath, listfile):
+    """dtu_yao.MVSDataset.build_list (:26-48): [(scan, light_idx, ref_view, src_views)], 7 light conditions
+    per viewpoint of the shared Cameras/pair.txt."""
+    metas = []
+    for scan in _read_scans(listfile):
+        for ref, src in _read_pairs(os.path.join(datapath, "Cameras/pair.txt")):
+            for light_idx in range(7):
+                metas.append((scan, light_idx, ref, src))
+    return metas

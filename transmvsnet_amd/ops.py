@@ -658,7 +658,71 @@ def depth_metrics(depth, depth_gt, mask, depth_interval):
     return out
 
 
-for _name in ("stage_hypotheses", "warp_corr", "aggregate_finalize", "homo_warping", "softmax_wta", "costregnet",
+EVAL_METRIC_NAMES = ("abs_depth_error", "thres2mm_error", "thres4mm_error", "thres8mm_error", "thres14mm_error",
+                     "thres20mm_error", "thres2mm_abserror", "thres4mm_abserror", "thres8mm_abserror",
+                     "thres14mm_abserror", "thres20mm_abserror", "thres>20mm_abserror")  # train.py:216-228
+
+
+def depth_eval_metrics(depth_est, depth_gt, mask, out=None):
+    """The twelve DTU validation scalars of train.py:216-228 (EVAL_METRIC_NAMES) -> device tensor [12]; no
+    host sync. `out`: a caller-provided contiguous float32 [12] (a row of a per-interval log buffer)."""
+    for t, n in ((depth_est, "depth_est"), (depth_gt, "depth_gt"), (mask, "mask"), (out, "out")):
+        _dev(t, n)
+    if depth_est.shape != depth_gt.shape or depth_est.shape != mask.shape:
+        raise ValueError("depth_est, depth_gt and mask must have one shape")
+    n = depth_est.numel()
+    nbytes = _lib_h().tmvs_depth_eval_metrics_workspace(n)
+    ws = torch.empty(nbytes // 8 + 8, dtype=torch.float64, device=depth_est.device)
+    if out is None:
+        out = torch.empty(12, device=depth_est.device)
+    elif tuple(out.shape) != (12,) or out.device != depth_est.device:
+        raise ValueError("depth_eval_metrics: out must be a contiguous [12] tensor on depth_est's device")
+    with _Span("tmvs_depth_eval_metrics"):
+        _lib.check(_lib_h().tmvs_depth_eval_metrics(_ptr(depth_est), _ptr(depth_gt), _ptr(mask), n, _ptr(ws),
+                                                    ws.numel() * 8, _ptr(out), _stream()), "tmvs_depth_eval_metrics")
+    return out
+
+
+def gt_pyramid(depth_raw, rows, cols, mode="bld", depth_min=0.0, depth_end=0.0, mask_png=None, target_hw=(512, 640)):
+    """tmvs_gt_pyramid: the raw depth map [h, w] (and, mode "dtu", the raw depth_visual PNG [h, w] uint8) ->
+    ({stage: depth}, {stage: mask}), float32 [H, W] maps at the three stage sizes. rows / cols: the int32
+    device tables of data.gt_pyramid_tables for this size and mode."""
+    if mode not in ("bld", "dtu"):
+        raise ValueError(f"gt_pyramid: mode must be 'bld' or 'dtu', got {mode!r}")
+    _dev(depth_raw, "depth_raw")
+    if depth_raw.dim() != 2:
+        raise ValueError("gt_pyramid: depth_raw must be [h, w]")
+    h, w = depth_raw.shape
+    for t, n in ((rows, "rows"), (cols, "cols")):
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.device != depth_raw.device:
+            raise RuntimeError(f"gt_pyramid: {n} must be a contiguous int32 tensor on depth_raw's device")
+    if mode == "dtu":
+        if mask_png is None or not mask_png.is_cuda or mask_png.dtype != torch.uint8 or not mask_png.is_contiguous() \
+                or tuple(mask_png.shape) != (h, w) or mask_png.device != depth_raw.device:
+            raise RuntimeError("gt_pyramid: mode 'dtu' needs mask_png, a contiguous uint8 [h, w] tensor on "
+                               "depth_raw's device")
+        h3, w3 = int(target_hw[0]), int(target_hw[1])
+        if h3 <= 0 or w3 <= 0 or h3 > h // 2 or w3 > w // 2:
+            raise ValueError(f"gt_pyramid: the crop {h3} x {w3} does not fit the halved image {h // 2} x {w // 2}")
+    else:
+        h3, w3 = h, w
+    if h3 < 4 or w3 < 4:
+        raise ValueError("gt_pyramid: the stage-3 size must be at least 4 x 4")
+    if rows.numel() != h3 + h3 // 2 + h3 // 4 or cols.numel() != w3 + w3 // 2 + w3 // 4:
+        raise ValueError("gt_pyramid: rows / cols do not hold one entry per output row / column of the 3 stages")
+    depth = {f"stage{3 - s}": torch.empty(h3 >> s, w3 >> s, device=depth_raw.device) for s in range(3)}
+    mask = {k: torch.empty_like(v) for k, v in depth.items()}
+    with _Span("tmvs_gt_pyramid"):
+        _lib.check(_lib_h().tmvs_gt_pyramid(_lib.GT_DTU if mode == "dtu" else _lib.GT_BLD, _ptr(depth_raw),
+                                            _ptr(mask_png if mode == "dtu" else None), h, w, h3, w3,
+                                            ctypes.c_float(depth_min), ctypes.c_float(depth_end), _ptr(rows),
+                                            _ptr(cols), _ptr(depth["stage3"]), _ptr(depth["stage2"]),
+                                            _ptr(depth["stage1"]), _ptr(mask["stage3"]), _ptr(mask["stage2"]),
+                                            _ptr(mask["stage1"]), _stream()), "tmvs_gt_pyramid")
+    return depth, mask
+
+
+for _name in ("depth_eval_metrics", "gt_pyramid", "stage_hypotheses", "warp_corr", "aggregate_finalize", "homo_warping", "softmax_wta", "costregnet",
               "costregnet_wta",
               "conv3d_bn_relu", "deconv3d_bn_relu_add", "fmt_embed", "fmt_kv", "fmt_apply", "fmt_pathway",
               "fmt_forward", "depth_stage", "deform_conv2d", "dcn_fused", "conv3x3_nhwc", "fpn_merge",

@@ -156,3 +156,110 @@ def stacked_features(n_views: int, height: int, width: int, seed: int = 2):
     g = torch.Generator(device="cpu").manual_seed(seed)
     return {name: torch.randn(1, n_views, c, height // s, width // s, generator=g)
             for name, c, s in (("stage1", 32, 4), ("stage2", 16, 2), ("stage3", 8, 1))}
+
+
+# ------------------------------------------------------------------ training scans on disk
+def _plane_view(K, E, height, width, plane=(0.02, -0.03, 1.0, 650.0)):
+    """A textured plane n . X = c (world frame) seen by the camera (K 3x3 at this pixel scale, E 4x4
+    world -> camera): (depth [h,w] float32, image [h,w,3] uint8)."""
+    n, c = np.asarray(plane[:3], np.float64), float(plane[3])
+    R, t = E[:3, :3].astype(np.float64), E[:3, 3].astype(np.float64)
+    y, x = np.meshgrid(np.arange(height, dtype=np.float64), np.arange(width, dtype=np.float64), indexing="ij")
+    rays = np.linalg.inv(K.astype(np.float64)) @ np.stack([x.ravel(), y.ravel(), np.ones(x.size)])
+    centre = -R.T @ t
+    dirs = R.T @ rays
+    s = (c - n @ centre) / (n @ dirs)  # camera-frame rays have z = 1, so the ray parameter is the depth
+    pts = centre[:, None] + dirs * s
+    tex = np.stack([0.5 + 0.5 * np.sin(pts[0] / f + p) * np.cos(pts[1] / g) for f, g, p in
+                    ((9.0, 13.0, 0.0), (17.0, 7.0, 1.0), (5.0, 23.0, 2.0))], axis=-1)
+    return (s.reshape(height, width).astype(np.float32),
+            np.clip(tex.reshape(height, width, 3) * 255.0, 0, 255).astype(np.uint8))
+
+
+def _write_cam(filename, extrinsic, intrinsic, depth_line):
+    with open(filename, "w") as f:
+        f.write("extrinsic\n")
+        for row in extrinsic:
+            f.write(" ".join("{:.9g}".format(float(v)) for v in row) + "\n")
+        f.write("\nintrinsic\n")
+        for row in intrinsic:
+            f.write(" ".join("{:.9g}".format(float(v)) for v in row) + "\n")
+        f.write("\n" + depth_line + "\n")
+
+
+def _write_pairs(filename, n_views):
+    with open(filename, "w") as f:
+        f.write(f"{n_views}\n")
+        for v in range(n_views):
+            others = [(v + k) % n_views for k in range(1, n_views)]
+            f.write(f"{v}\n{len(others)} " + " ".join(f"{o} {100.0 - i:.1f}" for i, o in enumerate(others)) + "\n")
+
+
+def write_blended_scan(root, scan="scan0", n_views=3, height=128, width=160, seed=1):
+    """A BlendedMVS-format scan as datasets/bld_train.py reads it, under root/scan: blended_images/*.jpg,
+    cams/*_cam.txt (full-size intrinsics = synthetic_cameras' x 4; depth line 'min interval n max'),
+    cams/pair.txt (every view with all others as sources) and rendered_depth_maps/*.pfm of a textured plane.
+    Writes root/list.txt and returns its path."""
+    import os
+
+    from PIL import Image
+
+    from .data import save_pfm
+    cams = synthetic_cameras(n_views, height, width, seed=seed)["stage1"][0].numpy()
+    for sub in ("blended_images", "cams", "rendered_depth_maps"):
+        os.makedirs(os.path.join(root, scan, sub), exist_ok=True)
+    for v in range(n_views):
+        K = cams[v, 1, :3, :3].copy()
+        K[:2] *= 4.0
+        depth, img = _plane_view(K, cams[v, 0], height, width)
+        Image.fromarray(img).save(os.path.join(root, scan, "blended_images", "{:0>8}.jpg".format(v)), quality=95)
+        save_pfm(os.path.join(root, scan, "rendered_depth_maps", "{:0>8}.pfm".format(v)), depth)
+        _write_cam(os.path.join(root, scan, "cams", "{:0>8}_cam.txt".format(v)), cams[v, 0], K,
+                   "{} {} {} {}".format(DTU_DEPTH_MIN, DTU_DEPTH_INTERVAL, DTU_NDEPTH, 935.0))
+    _write_pairs(os.path.join(root, scan, "cams", "pair.txt"), n_views)
+    listfile = os.path.join(root, "list.txt")
+    with open(listfile, "w") as f:
+        f.write(scan + "\n")
+    return listfile
+
+
+def write_dtu_train_scan(root, scan="scan1", n_views=3, height=128, width=160, margin=(12, 12), seed=1):
+    """A dtu_yao-format training set (datasets/dtu_yao.py) with one scan: Rectified/{scan}_train/
+    rect_{vid+1:03}_{light}_r5000.png at height x width (7 lights), Cameras/train/*_cam.txt (intrinsics as
+    stored), Cameras/pair.txt, and Depths_raw/{scan}/depth_map_*.pfm + depth_visual_*.png at the raw size
+    2 * (height + margin[0]) x 2 * (width + margin[1]), whose halved centre crop is height x width. Writes
+    root/list.txt and returns its path."""
+    import os
+
+    from PIL import Image
+
+    from .data import save_pfm
+    cams = synthetic_cameras(n_views, height, width, seed=seed)["stage1"][0].numpy()
+    for sub in (f"Rectified/{scan}_train", "Cameras/train", f"Depths_raw/{scan}"):
+        os.makedirs(os.path.join(root, sub), exist_ok=True)
+    rh, rw = 2 * (height + margin[0]), 2 * (width + margin[1])
+    for v in range(n_views):
+        K3 = cams[v, 1, :3, :3].copy()
+        K3[:2] *= 4.0  # the image's own scale
+        _, img = _plane_view(K3, cams[v, 0], height, width)
+        for light in range(7):
+            lit = np.clip(img.astype(np.float32) * (0.7 + 0.05 * light), 0, 255).astype(np.uint8)
+            Image.fromarray(lit).save(os.path.join(root, f"Rectified/{scan}_train",
+                                                   "rect_{:0>3}_{}_r5000.png".format(v + 1, light)))
+        # the raw map: twice the image's scale, its centre moved by the crop's start
+        Kr = K3.copy()
+        Kr[:2] *= 2.0
+        Kr[0, 2] += 2.0 * (margin[1] // 2)
+        Kr[1, 2] += 2.0 * (margin[0] // 2)
+        depth, _ = _plane_view(Kr, cams[v, 0], rh, rw)
+        save_pfm(os.path.join(root, f"Depths_raw/{scan}", "depth_map_{:0>4}.pfm".format(v)), depth)
+        visual = np.full((rh, rw), 128, np.uint8)
+        visual[:rh // 8], visual[:, :rw // 8] = 0, 10  # a border outside the mask (0 and exactly 10: not > 10)
+        Image.fromarray(visual).save(os.path.join(root, f"Depths_raw/{scan}", "depth_visual_{:0>4}.png".format(v)))
+        _write_cam(os.path.join(root, "Cameras/train", "{:0>8}_cam.txt".format(v)), cams[v, 0], cams[v, 1, :3, :3],
+                   "{} {}".format(DTU_DEPTH_MIN, DTU_DEPTH_INTERVAL))
+    _write_pairs(os.path.join(root, "Cameras/pair.txt"), n_views)
+    listfile = os.path.join(root, "list.txt")
+    with open(listfile, "w") as f:
+        f.write(scan + "\n")
+    return listfile

@@ -803,6 +803,60 @@ class FlatAdam:
         device counter, so that counter is the only count from then on (one host sync to read)."""
         return int(self._step_dev.item()) if self._graphed else self._host_steps
 
+    def state_dict(self):
+        """torch.optim.Adam.state_dict()'s layout, so the 'optimizer' entry of a checkpoint written here
+        loads into the reference's optim.Adam (finetune.py:337) and back: state {i: {'step', 'exp_avg',
+        'exp_avg_sq'}} in parameter order (= filter(requires_grad, model.parameters()) when built from it),
+        the moments as copies in each parameter's shape, 'step' a float32 scalar tensor (step_count; one host
+        sync after a captured step), and one param_groups entry."""
+        step = float(self.step_count)
+        state = {}
+        if step > 0:  # torch creates a parameter's state at its first step
+            for i, (p, (off, k)) in enumerate(zip(self.params, self._segs)):
+                state[i] = {"step": torch.tensor(step, dtype=torch.float32),
+                            "exp_avg": self.exp_avg[off:off + k].view_as(p).clone(),
+                            "exp_avg_sq": self.exp_avg_sq[off:off + k].view_as(p).clone()}
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
+                 "fused": None, "params": list(range(len(self.params)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, state_dict):
+        """The inverse of state_dict(), also for an 'optimizer' entry torch.optim.Adam wrote over the same
+        parameters (one param group; 'step' an int or a tensor). Sets the moments, lr / betas / eps /
+        weight_decay and both step counters (host and device). A parameter without state (torch: it never
+        had a gradient) gets zero moments; the stated steps must agree, since this optimizer has one."""
+        groups = state_dict["param_groups"]
+        if len(groups) != 1:
+            raise ValueError(f"FlatAdam.load_state_dict: one param group expected, got {len(groups)}")
+        group = groups[0]
+        ids = list(group["params"])
+        if len(ids) != len(self.params):
+            raise ValueError(f"FlatAdam.load_state_dict: {len(ids)} parameters in the state, {len(self.params)} here")
+        if group.get("amsgrad", False) or group.get("maximize", False):
+            raise ValueError("FlatAdam.load_state_dict: amsgrad / maximize are not supported")
+        state = state_dict["state"]
+        steps = set()
+        with torch.no_grad():
+            for pid, p, (off, k) in zip(ids, self.params, self._segs):
+                st = state.get(pid)
+                if st is None:
+                    self.exp_avg[off:off + k].zero_()
+                    self.exp_avg_sq[off:off + k].zero_()
+                    continue
+                for name, flat in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+                    if tuple(st[name].shape) != tuple(p.shape):
+                        raise ValueError(f"FlatAdam.load_state_dict: {name} of parameter {pid} is "
+                                         f"{list(st[name].shape)}, the parameter {list(p.shape)}")
+                    flat[off:off + k].copy_(st[name].reshape(-1))
+                steps.add(int(float(st["step"])))
+        if len(steps) > 1:
+            raise ValueError(f"FlatAdam.load_state_dict: the parameters' step counts differ ({sorted(steps)})")
+        self.lr, self.betas = float(group["lr"]), tuple(float(b) for b in group["betas"])
+        self.eps, self.weight_decay = float(group["eps"]), float(group["weight_decay"])
+        self._host_steps = steps.pop() if steps else 0
+        self._step_dev.fill_(self._host_steps)
+
     def step(self, lr=None):
         self._gather()
         lr = self.lr if lr is None else lr
