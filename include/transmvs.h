@@ -350,6 +350,25 @@ int tmvs_pixelwise_train_backward(const float* sims, int n_views, int ndepth, in
                                   const float* stats, const float* view_w, const int* dstar, const float* dview_w,
                                   void* workspace, size_t workspace_bytes, float* dsims, float* dpwp, void* stream);
 
+/* The PixelwiseNet pair for a batch of `batch` samples (train.py's BATCH_SIZE > 1): the reference calls
+ * PixelwiseNet per source view on [B,1,D,h,w] (TransMVSNet.py:71-77), so each view's BatchNorm statistics
+ * are joint over the B*D*H*W elements of that view in all samples, and the BatchNorm backward's 1/N is
+ * 1/(B*D*H*W).
+ *   sims, dsims [B][V][D][H][W]; stats [V][48], one row per view, shared by the batch; view_w, dstar,
+ *   dview_w [B][V][H][W]; dpwp [201] (accumulated: zero it first); the workspace is
+ *   tmvs_pixelwise_train_workspace(), whatever the batch.
+ * The launches per view do not grow with batch; reductions as above (deterministic). With batch 1 they
+ * are tmvs_pixelwise_train_forward / _backward bit for bit (those run the same kernels). B*H*W of 2^31 - 256
+ * or more: TMVS_ERR_SHAPE. Additions: no earlier signature or behaviour changes with them, so
+ * TMVS_ABI_VERSION stays as it was. */
+int tmvs_pixelwise_train_forward_batched(const float* sims, int batch, int n_views, int ndepth, int height, int width,
+                                         const float* pwp, void* workspace, size_t workspace_bytes, float* stats,
+                                         float* view_w, int* dstar, void* stream);
+int tmvs_pixelwise_train_backward_batched(const float* sims, int batch, int n_views, int ndepth, int height, int width,
+                                          const float* pwp, const float* stats, const float* view_w, const int* dstar,
+                                          const float* dview_w, void* workspace, size_t workspace_bytes, float* dsims,
+                                          float* dpwp, void* stream);
+
 /* FMT_with_pathway lateral step for training (FMT.py:201-209, 221-228), NHWC, C in {8, 16}:
  *   tmvs_upsample2_add_nhwc: u [n][2h][2w][C] = bilinear x2 (align_corners=False) of r [n][h][w][C]
  *     + lateral [n][C][2h][2w] (NCHW);  tmvs_upsample2_backward_nhwc: dr [n][h][w][C] = the adjoint

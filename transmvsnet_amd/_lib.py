@@ -77,6 +77,8 @@ SIGNATURES = {
     "tmvs_aggregate_train": (I, [P, P, I, I, I, I, I, P, P, P]),
     "tmvs_aggregate_train_backward": (I, [P, P, P, P, P, I, I, I, I, I, P, P, P]),
     "tmvs_pixelwise_train_backward": (I, [P, I, I, I, I, P, P, P, P, P, P, S, P, P, P]),
+    "tmvs_pixelwise_train_forward_batched": (I, [P, I, I, I, I, I, P, P, S, P, P, P, P]),
+    "tmvs_pixelwise_train_backward_batched": (I, [P, I, I, I, I, I, P, P, P, P, P, P, S, P, P, P]),
     "tmvs_upsample2_add_nhwc": (I, [P, P, I, I, I, I, P, P]),
     "tmvs_upsample2_backward_nhwc": (I, [P, I, I, I, I, P, P]),
     "tmvs_token_linear": (I, [P, L, I, I, P, P, I, P, I, P, P]),

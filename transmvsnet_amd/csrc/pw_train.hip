@@ -3,8 +3,11 @@
 // + BatchNorm3d + ReLU, 16->8 + BatchNorm3d + ReLU, 8->1 + bias, sigmoid, max over D) and :71-93
 // (sim = sum_v w_v sim_v / (1e-5 + sum_v w_v), views in order).
 //
-// One sample; per-view similarity volumes sims [V][D][P] (P = H*W). PixelwiseNet runs per view
-// with BatchNorm batch statistics over that view's D*P elements (the reference calls it per view).
+// A batch of B samples; per-view similarity volumes sims [B][V][D][P] (P = H*W). PixelwiseNet runs per
+// view on that view's [B,1,D,h,w] volume (models/TransMVSNet.py:71-77), so its BatchNorm batch statistics
+// are joint over the B*D*P elements of the view's B chunks, which lie V*D*P floats apart: every pass walks
+// the view's elements in (sample, depth, pixel) order through a BatchWalk, one launch whatever B is. The
+// single-sample entry points are the B = 1 case of the same kernels.
 // Parameters (device, fp32, "pwp"): w0[16] g0[16] b0[16] W1[8][16] g1[8] b1[8] w2[8] b2 (201).
 // Per-view statistics ("st", fp32): mean0[16] var0[16] mean1[8] var1[8] (biased variances).
 // Every reduction is fp64 block partials + a fixed-order combine (deterministic, no atomics);
@@ -17,6 +20,20 @@ constexpr int kPwBlock = 256;
 constexpr int PW_W0 = 0, PW_G0 = 16, PW_B0 = 32, PW_W1 = 48, PW_G1 = 176, PW_B1 = 184, PW_W2 = 192, PW_B2 = 200;
 constexpr int ST_M0 = 0, ST_V0 = 16, ST_M1 = 32, ST_V1 = 40;
 constexpr float kPwEps = 1e-5f;
+
+// A thread's walk over the rows [i0, i1) of a view's batch, 256 rows per step: row i is row r = i % n of
+// sample b = i / n (n rows per sample: D*P elements or P pixels). One division at the start, then carries.
+struct BatchWalk {
+  long n, b, r;
+  __device__ __forceinline__ BatchWalk(long i, long n_) : n(n_), b(i / n_), r(i - (i / n_) * n_) {}
+  __device__ __forceinline__ void step() {
+    r += kPwBlock;
+    while (r >= n) {
+      r -= n;
+      ++b;
+    }
+  }
+};
 
 struct PwChain {  // one element's forward chain
   float y0[16], pre1[8], y1[8], xhat1[8];
@@ -69,12 +86,15 @@ __device__ __forceinline__ void pw_chain(float s, const float* __restrict__ p, c
 
 // ---------------------------------------------------------------- forward
 // stats of s (sum, sum^2) -> layer-0 statistics mean0 = w0*mean_s, var0 = w0^2 * var_s
-__global__ __launch_bounds__(kPwBlock) void pw_s_partial_kernel(const float* __restrict__ s, long n, long vpb,
+// (s: the view's chunk of sample 0; sample b's is b * bstride floats on; n = D*P per sample, tot = B*n)
+__global__ __launch_bounds__(kPwBlock) void pw_s_partial_kernel(const float* __restrict__ s, long n, long tot,
+                                                                long bstride, long vpb,
                                                                 double* __restrict__ partial) {
-  const long i0 = (long)blockIdx.x * vpb, i1 = i0 + vpb < n ? i0 + vpb : n;
+  const long i0 = (long)blockIdx.x * vpb, i1 = i0 + vpb < tot ? i0 + vpb : tot;
   double v[2] = {0.0, 0.0};
-  for (long i = i0 + threadIdx.x; i < i1; i += kPwBlock) {
-    const double x = (double)s[i];
+  BatchWalk k(i0 + threadIdx.x, n);
+  for (long i = i0 + threadIdx.x; i < i1; i += kPwBlock, k.step()) {
+    const double x = (double)s[k.b * bstride + k.r];
     v[0] += x;
     v[1] += x * x;
   }
@@ -93,17 +113,19 @@ __global__ void pw_stats0_kernel(const double* __restrict__ sums, long n, const 
   st[ST_V0 + j] = (float)(w * w * var);
 }
 
-__global__ __launch_bounds__(kPwBlock) void pw_z1_partial_kernel(const float* __restrict__ s, long n, long vpb,
+__global__ __launch_bounds__(kPwBlock) void pw_z1_partial_kernel(const float* __restrict__ s, long n, long tot,
+                                                                 long bstride, long vpb,
                                                                  const float* __restrict__ p,
                                                                  const float* __restrict__ st,
                                                                  double* __restrict__ partial) {
-  const long i0 = (long)blockIdx.x * vpb, i1 = i0 + vpb < n ? i0 + vpb : n;
+  const long i0 = (long)blockIdx.x * vpb, i1 = i0 + vpb < tot ? i0 + vpb : tot;
   double v[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) v[k] = 0.0;
-  for (long i = i0 + threadIdx.x; i < i1; i += kPwBlock) {
+  BatchWalk wk(i0 + threadIdx.x, n);
+  for (long i = i0 + threadIdx.x; i < i1; i += kPwBlock, wk.step()) {
     float y0[16], z1[8];
-    pw_layer0(s[i], p, st, y0, z1);
+    pw_layer0(s[wk.b * bstride + wk.r], p, st, y0, z1);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       v[k] += (double)z1[k];
@@ -122,12 +144,18 @@ __global__ void pw_stats1_kernel(const double* __restrict__ sums, long n, float*
   st[ST_V1 + k] = (float)(var > 0.0 ? var : 0.0);
 }
 
-// view weight w[p] = max_d sigmoid(PixelwiseNet(s[d][p])) and its (first) argmax
-__global__ __launch_bounds__(kPwBlock) void pw_weight_kernel(const float* __restrict__ s, int D, int P,
+// view weight w[p] = max_d sigmoid(PixelwiseNet(s[d][p])) and its (first) argmax, over the B*P pixels of
+// the view's batch (sample b's volume b * bstride floats, its maps b * wstride floats on)
+__global__ __launch_bounds__(kPwBlock) void pw_weight_kernel(const float* __restrict__ s, int B, int D, int P,
+                                                             long bstride, long wstride,
                                                              const float* __restrict__ p, const float* __restrict__ st,
                                                              float* __restrict__ w, int* __restrict__ dstar) {
-  const int q = blockIdx.x * kPwBlock + threadIdx.x;
-  if (q >= P) return;
+  const int bq = blockIdx.x * kPwBlock + threadIdx.x;
+  if (bq >= B * P) return;
+  const int b = bq / P, q = bq - b * P;
+  s += (size_t)b * bstride;
+  w += (size_t)b * wstride;
+  dstar += (size_t)b * wstride;
   float best = 0.f;
   int bi = 0;
   for (int d = 0; d < D; ++d) {
@@ -204,17 +232,21 @@ __global__ __launch_bounds__(kPwBlock) void aggregate_backward_kernel(
 __global__ __launch_bounds__(kPwBlock) void pw_bwd1_kernel(const float* __restrict__ s, int D, int P,
                                                            const float* __restrict__ p, const float* __restrict__ st,
                                                            const float* __restrict__ w, const int* __restrict__ dstar,
-                                                           const float* __restrict__ dw, long ppb,
+                                                           const float* __restrict__ dw, int B, long bstride,
+                                                           long wstride, long ppb,
                                                            double* __restrict__ partial) {
   double v[25];
 #pragma unroll
   for (int i = 0; i < 25; ++i) v[i] = 0.0;
-  const long q0 = (long)blockIdx.x * ppb, q1 = q0 + ppb < P ? q0 + ppb : P;
-  for (long q = q0 + threadIdx.x; q < q1; q += kPwBlock) {
+  const long tot = (long)B * P;
+  const long q0 = (long)blockIdx.x * ppb, q1 = q0 + ppb < tot ? q0 + ppb : tot;
+  BatchWalk wk(q0 + threadIdx.x, P);
+  for (long bq = q0 + threadIdx.x; bq < q1; bq += kPwBlock, wk.step()) {
+    const long q = wk.r, m = wk.b * wstride + q;  // the pixel, and its place in the [B][V][P] maps
     PwChain c;
-    pw_chain(s[(size_t)dstar[q] * P + q], p, st, c);
-    const float sg = w[q];
-    const float go = dw[q] * ((1.f - sg) * sg);  // sigmoid backward at the argmax
+    pw_chain(s[wk.b * bstride + (size_t)dstar[m] * P + q], p, st, c);
+    const float sg = w[m];
+    const float go = dw[m] * ((1.f - sg) * sg);  // sigmoid backward at the argmax
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const float g1 = c.pre1[k] > 0.f ? go * p[PW_W2 + k] : 0.f;
@@ -249,20 +281,23 @@ __global__ __launch_bounds__(kPwBlock) void pw_bwd2_kernel(const float* __restri
                                                            const float* __restrict__ p, const float* __restrict__ st,
                                                            const float* __restrict__ w, const int* __restrict__ dstar,
                                                            const float* __restrict__ dw, const double* __restrict__ s1,
-                                                           long epb, double* __restrict__ partial) {
-  const long n = (long)D * P;
-  const double inv_n = 1.0 / (double)n;
+                                                           int B, long bstride, long wstride, long epb,
+                                                           double* __restrict__ partial) {
+  const long n = (long)D * P, tot = (long)B * n;
+  const double inv_n = 1.0 / (double)tot;  // the BatchNorm's count: the view's whole batch
   float acc[160];  // g0 sums [0,16), g0*xhat0 sums [16,32), dW1 [32,160)
 #pragma unroll
   for (int i = 0; i < 160; ++i) acc[i] = 0.f;
-  const long e0 = (long)blockIdx.x * epb, e1 = e0 + epb < n ? e0 + epb : n;
-  for (long e = e0 + threadIdx.x; e < e1; e += kPwBlock) {
-    const int d = (int)(e / P), q = (int)(e - (long)d * P);
-    const float sg = w[q];
-    const float go = dw[q] * ((1.f - sg) * sg);
+  const long e0 = (long)blockIdx.x * epb, e1 = e0 + epb < tot ? e0 + epb : tot;
+  BatchWalk wk(e0 + threadIdx.x, n);
+  for (long e = e0 + threadIdx.x; e < e1; e += kPwBlock, wk.step()) {
+    const int d = (int)(wk.r / P), q = (int)(wk.r - (long)d * P);
+    const long m = wk.b * wstride + q;
+    const float sg = w[m];
+    const float go = dw[m] * ((1.f - sg) * sg);
     float y0[16], pre0[16], dz1[8];
-    const float sv = s[e];
-    pw_dz1(sv, d, dstar[q], go, p, st, s1, inv_n, y0, pre0, dz1);
+    const float sv = s[wk.b * bstride + wk.r];
+    pw_dz1(sv, d, dstar[m], go, p, st, s1, inv_n, y0, pre0, dz1);
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       float dy0 = 0.f;
@@ -287,21 +322,24 @@ __global__ __launch_bounds__(kPwBlock) void pw_bwd3_kernel(const float* __restri
                                                            const float* __restrict__ p, const float* __restrict__ st,
                                                            const float* __restrict__ w, const int* __restrict__ dstar,
                                                            const float* __restrict__ dw, const double* __restrict__ s1,
-                                                           const double* __restrict__ s2, long epb,
+                                                           const double* __restrict__ s2, int B, long bstride,
+                                                           long wstride, long epb,
                                                            float* __restrict__ dsims, double* __restrict__ partial) {
-  const long n = (long)D * P;
-  const double inv_n = 1.0 / (double)n;
+  const long n = (long)D * P, tot = (long)B * n;
+  const double inv_n = 1.0 / (double)tot;
   double v[16];
 #pragma unroll
   for (int j = 0; j < 16; ++j) v[j] = 0.0;
-  const long e0 = (long)blockIdx.x * epb, e1 = e0 + epb < n ? e0 + epb : n;
-  for (long e = e0 + threadIdx.x; e < e1; e += kPwBlock) {
-    const int d = (int)(e / P), q = (int)(e - (long)d * P);
-    const float sg = w[q];
-    const float go = dw[q] * ((1.f - sg) * sg);
+  const long e0 = (long)blockIdx.x * epb, e1 = e0 + epb < tot ? e0 + epb : tot;
+  BatchWalk wk(e0 + threadIdx.x, n);
+  for (long e = e0 + threadIdx.x; e < e1; e += kPwBlock, wk.step()) {
+    const int d = (int)(wk.r / P), q = (int)(wk.r - (long)d * P);
+    const long m = wk.b * wstride + q, at = wk.b * bstride + wk.r;
+    const float sg = w[m];
+    const float go = dw[m] * ((1.f - sg) * sg);
     float y0[16], pre0[16], dz1[8];
-    const float sv = s[e];
-    pw_dz1(sv, d, dstar[q], go, p, st, s1, inv_n, y0, pre0, dz1);
+    const float sv = s[at];
+    pw_dz1(sv, d, dstar[m], go, p, st, s1, inv_n, y0, pre0, dz1);
     float ds = 0.f;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
@@ -316,7 +354,7 @@ __global__ __launch_bounds__(kPwBlock) void pw_bwd3_kernel(const float* __restri
       ds = fmaf(p[PW_W0 + j], dz0, ds);
       v[j] += (double)dz0 * (double)sv;
     }
-    dsims[e] = dsims[e] + ds;
+    dsims[at] = dsims[at] + ds;
   }
   block_sum_store<true>(v, partial + (size_t)blockIdx.x * 16);
 }
@@ -356,33 +394,57 @@ using namespace tmvs;
 // workspace: partials (<= 1024 blocks x 160 doubles) + sums (2 + 16 + 25 + 160 + 16 doubles)
 extern "C" size_t tmvs_pixelwise_train_workspace(void) { return (1024 * 160 + 256) * sizeof(double) + 256; }
 
-extern "C" int tmvs_pixelwise_train_forward(const float* sims, int n_views, int ndepth, int height, int width,
-                                            const float* pwp, void* workspace, size_t workspace_bytes, float* stats,
-                                            float* view_w, int* dstar, void* stream) {
-  if (!sims || !pwp || !workspace || !stats || !view_w || !dstar || n_views <= 0 || ndepth <= 0 || height <= 0 ||
-      width <= 0)
+// A batch's counts as the kernels index them: B*P pixels and the [B][V][D][P] volume's floats in int / long
+static bool pw_batch_fits(int batch, int n_views, int ndepth, int height, int width) {
+  const long P = (long)height * width;
+  return batch * P < (1L << 31) - kPwBlock && (double)batch * n_views * ndepth * (double)P < 9e18;
+}
+
+static int pw_forward(const float* sims, int batch, int n_views, int ndepth, int height, int width, const float* pwp,
+                      void* workspace, size_t workspace_bytes, float* stats, float* view_w, int* dstar, void* stream) {
+  if (!sims || !pwp || !workspace || !stats || !view_w || !dstar || batch <= 0 || n_views <= 0 || ndepth <= 0 ||
+      height <= 0 || width <= 0)
     return TMVS_ERR_ARG;
   if (workspace_bytes < tmvs_pixelwise_train_workspace()) return TMVS_ERR_ARG;
+  if (!pw_batch_fits(batch, n_views, ndepth, height, width)) return TMVS_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int P = height * width;
-  const long n = (long)ndepth * P;
+  const long n = (long)ndepth * P, tot = (long)batch * n;
+  const long bstride = (long)n_views * n, wstride = (long)n_views * P;  // sample to sample
   double* part = (double*)workspace;
   double* sums = part + 1024 * 160;
-  const auto [c, nb] = pw_chunk(n);
+  const auto [c, nb] = pw_chunk(tot);
   for (int v = 0; v < n_views; ++v) {
     const float* s = sims + (size_t)v * n;
     float* sv = stats + (size_t)v * 48;
-    hipLaunchKernelGGL(pw_s_partial_kernel, dim3(nb), dim3(kPwBlock), 0, st, s, n, c, part);
+    hipLaunchKernelGGL(pw_s_partial_kernel, dim3(nb), dim3(kPwBlock), 0, st, s, n, tot, bstride, c, part);
     hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(2), dim3(kPwBlock), 0, st, (const double*)part, nb, 2, sums);
-    hipLaunchKernelGGL(pw_stats0_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, n, pwp, sv);
-    hipLaunchKernelGGL(pw_z1_partial_kernel, dim3(nb), dim3(kPwBlock), 0, st, s, n, c, pwp, (const float*)sv, part);
+    hipLaunchKernelGGL(pw_stats0_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, tot, pwp, sv);
+    hipLaunchKernelGGL(pw_z1_partial_kernel, dim3(nb), dim3(kPwBlock), 0, st, s, n, tot, bstride, c, pwp,
+                       (const float*)sv, part);
     hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(16), dim3(kPwBlock), 0, st, (const double*)part, nb, 16, sums);
-    hipLaunchKernelGGL(pw_stats1_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, n, sv);
-    hipLaunchKernelGGL(pw_weight_kernel, dim3((P + kPwBlock - 1) / kPwBlock), dim3(kPwBlock), 0, st, s, ndepth, P,
-                       pwp, (const float*)sv, view_w + (size_t)v * P, dstar + (size_t)v * P);
+    hipLaunchKernelGGL(pw_stats1_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, tot, sv);
+    hipLaunchKernelGGL(pw_weight_kernel, dim3((batch * P + kPwBlock - 1) / kPwBlock), dim3(kPwBlock), 0, st, s, batch,
+                       ndepth, P, bstride, wstride, pwp, (const float*)sv, view_w + (size_t)v * P,
+                       dstar + (size_t)v * P);
     TMVS_CHECK_LAUNCH();
   }
   return TMVS_OK;
+}
+
+extern "C" int tmvs_pixelwise_train_forward(const float* sims, int n_views, int ndepth, int height, int width,
+                                            const float* pwp, void* workspace, size_t workspace_bytes, float* stats,
+                                            float* view_w, int* dstar, void* stream) {
+  return pw_forward(sims, 1, n_views, ndepth, height, width, pwp, workspace, workspace_bytes, stats, view_w, dstar,
+                    stream);
+}
+
+extern "C" int tmvs_pixelwise_train_forward_batched(const float* sims, int batch, int n_views, int ndepth, int height,
+                                                    int width, const float* pwp, void* workspace,
+                                                    size_t workspace_bytes, float* stats, float* view_w, int* dstar,
+                                                    void* stream) {
+  return pw_forward(sims, batch, n_views, ndepth, height, width, pwp, workspace, workspace_bytes, stats, view_w, dstar,
+                    stream);
 }
 
 extern "C" int tmvs_aggregate_train(const float* sims, const float* view_w, int n_views, int ndepth, int height,
@@ -412,40 +474,59 @@ extern "C" int tmvs_aggregate_train_backward(const float* dsim, const float* sim
   return TMVS_OK;
 }
 
-extern "C" int tmvs_pixelwise_train_backward(const float* sims, int n_views, int ndepth, int height, int width,
-                                             const float* pwp, const float* stats, const float* view_w,
-                                             const int* dstar, const float* dview_w, void* workspace,
-                                             size_t workspace_bytes, float* dsims, float* dpwp, void* stream) {
-  if (!sims || !pwp || !stats || !view_w || !dstar || !dview_w || !workspace || !dsims || !dpwp || n_views <= 0 ||
-      ndepth <= 0 || height <= 0 || width <= 0)
+static int pw_backward(const float* sims, int batch, int n_views, int ndepth, int height, int width, const float* pwp,
+                       const float* stats, const float* view_w, const int* dstar, const float* dview_w,
+                       void* workspace, size_t workspace_bytes, float* dsims, float* dpwp, void* stream) {
+  if (!sims || !pwp || !stats || !view_w || !dstar || !dview_w || !workspace || !dsims || !dpwp || batch <= 0 ||
+      n_views <= 0 || ndepth <= 0 || height <= 0 || width <= 0)
     return TMVS_ERR_ARG;
   if (workspace_bytes < tmvs_pixelwise_train_workspace()) return TMVS_ERR_ARG;
+  if (!pw_batch_fits(batch, n_views, ndepth, height, width)) return TMVS_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int P = height * width;
   const long n = (long)ndepth * P;
+  const long bstride = (long)n_views * n, wstride = (long)n_views * P;
   double* part = (double*)workspace;
   double* s1 = part + 1024 * 160;
   double* s2 = s1 + 32;
   double* s3 = s2 + 160;
-  const auto [cp, nbp] = pw_chunk(P);
-  const auto [ce, nbe] = pw_chunk(n);
+  const auto [cp, nbp] = pw_chunk((long)batch * P);
+  const auto [ce, nbe] = pw_chunk((long)batch * n);
   for (int v = 0; v < n_views; ++v) {
     const float* s = sims + (size_t)v * n;
     const float* sv = stats + (size_t)v * 48;
     const float* w = view_w + (size_t)v * P;
     const int* ds = dstar + (size_t)v * P;
     const float* dw = dview_w + (size_t)v * P;
-    hipLaunchKernelGGL(pw_bwd1_kernel, dim3(nbp), dim3(kPwBlock), 0, st, s, ndepth, P, pwp, sv, w, ds, dw, cp, part);
+    hipLaunchKernelGGL(pw_bwd1_kernel, dim3(nbp), dim3(kPwBlock), 0, st, s, ndepth, P, pwp, sv, w, ds, dw, batch,
+                       bstride, wstride, cp, part);
     hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(25), dim3(kPwBlock), 0, st, (const double*)part, nbp, 25, s1);
     hipLaunchKernelGGL(pw_bwd2_kernel, dim3(nbe), dim3(kPwBlock), 0, st, s, ndepth, P, pwp, sv, w, ds, dw,
-                       (const double*)s1, ce, part);
+                       (const double*)s1, batch, bstride, wstride, ce, part);
     hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(160), dim3(kPwBlock), 0, st, (const double*)part, nbe, 160, s2);
     hipLaunchKernelGGL(pw_bwd3_kernel, dim3(nbe), dim3(kPwBlock), 0, st, s, ndepth, P, pwp, sv, w, ds, dw,
-                       (const double*)s1, (const double*)s2, ce, dsims + (size_t)v * n, part);
+                       (const double*)s1, (const double*)s2, batch, bstride, wstride, ce, dsims + (size_t)v * n, part);
     hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(16), dim3(kPwBlock), 0, st, (const double*)part, nbe, 16, s3);
     hipLaunchKernelGGL(pw_grad_finalize_kernel, dim3(1), dim3(128), 0, st, (const double*)s1, (const double*)s2,
                        (const double*)s3, dpwp);
     TMVS_CHECK_LAUNCH();
   }
   return TMVS_OK;
+}
+
+extern "C" int tmvs_pixelwise_train_backward(const float* sims, int n_views, int ndepth, int height, int width,
+                                             const float* pwp, const float* stats, const float* view_w,
+                                             const int* dstar, const float* dview_w, void* workspace,
+                                             size_t workspace_bytes, float* dsims, float* dpwp, void* stream) {
+  return pw_backward(sims, 1, n_views, ndepth, height, width, pwp, stats, view_w, dstar, dview_w, workspace,
+                     workspace_bytes, dsims, dpwp, stream);
+}
+
+extern "C" int tmvs_pixelwise_train_backward_batched(const float* sims, int batch, int n_views, int ndepth, int height,
+                                                     int width, const float* pwp, const float* stats,
+                                                     const float* view_w, const int* dstar, const float* dview_w,
+                                                     void* workspace, size_t workspace_bytes, float* dsims,
+                                                     float* dpwp, void* stream) {
+  return pw_backward(sims, batch, n_views, ndepth, height, width, pwp, stats, view_w, dstar, dview_w, workspace,
+                     workspace_bytes, dsims, dpwp, stream);
 }

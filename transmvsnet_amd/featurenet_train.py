@@ -8,6 +8,13 @@ statistics are updated once per view, in view order, momentum 0.1, unbiased vari
 stage features NCHW (stage1 [N,32,H/4,W/4], stage2 [N,16,H/2,W/2], stage3 [N,8,H,W]),
 differentiable w.r.t. every FeatureNet parameter (the image needs no gradient).
 
+A batch imgs [B,N,3,H,W] (train.py's BATCH_SIZE > 1) follows the same lines of the reference: FeatureNet is
+called once per view with that view's B images, so each BatchNorm2d takes its statistics over B*h*w per
+channel for that view alone, the running statistics are updated once per view in view order with the
+unbiased variance's n = B*h*w, and num_batches_tracked goes up by N. The images are laid out view-major,
+[N][B][h][w][C], so that a view's B images are one contiguous group of the grouped BatchNorm kernels;
+convolutions, DCNs and FPN merges are per image, and the weight gradients sum over all N*B images.
+
 Forward: the inference kernels without their folded BatchNorm -- tmvs_conv2d_bn_relu (trunk and the
 stage-1 head's 1x1), tmvs_conv3x3_nhwc (stage-2/3 heads' 3x3), tmvs_fpn_merge, and each DCN as ONE
 tmvs_dcn_forward_train launch (offset/mask conv + deformable conv, also writing the offset/mask
@@ -220,21 +227,31 @@ class _Tape:
 
     def __init__(self, n_views):
         self.n = n_views
-        self.stats = []  # (bn module, (mean [N, C], var [N, C]) per view, pixels per view)
+        self.stats = []  # (bn module, (mean [N, C], var [N, C]) per view, pixels per view: B * h * w)
+
+
+def _by_view(z, n_views):
+    """z [N*B,h,w,C], images view-major -> [N, B*h*w, C]: a view's B images as one BatchNorm group (a view of
+    the same memory; z itself when B = 1 would do, the kernels only read the group and channel counts)."""
+    return z.view(n_views, -1, z.shape[-1])
 
 
 def _bn_relu_views(tape, z, bn):
-    """relu(BatchNorm_train(z)) with statistics per view (z [N,h,w,C] NHWC): one grouped launch each
-    for the statistics and the normalisation (group = view)."""
-    mean, var = ops.bn_stats_grouped(z)
-    y = ops.bn_relu_train_grouped(z, mean, var, bn.weight.detach(), bn.bias.detach(), bn.eps)
-    tape.stats.append((bn, (mean, var), z.shape[1] * z.shape[2]))
+    """relu(BatchNorm_train(z)) with statistics per view over that view's B images (z [N*B,h,w,C] NHWC,
+    view-major): one grouped launch each for the statistics and the normalisation (group = view)."""
+    zv = _by_view(z, tape.n)
+    mean, var = ops.bn_stats_grouped(zv)
+    y = ops.bn_relu_train_grouped(zv, mean, var, bn.weight.detach(), bn.bias.detach(), bn.eps).view(z.shape)
+    tape.stats.append((bn, (mean, var), zv.shape[1]))
     return y, (mean, var)
 
 
 def _bn_relu_views_backward(dy, z, per, bn):
     mean, var = per
-    return ops.bn_relu_backward_grouped(dy.contiguous(), z, mean, var, bn.weight.detach(), bn.bias.detach(), bn.eps)
+    n = mean.shape[0]
+    dz, dg, db = ops.bn_relu_backward_grouped(_by_view(dy.contiguous(), n), _by_view(z, n), mean, var,
+                                              bn.weight.detach(), bn.bias.detach(), bn.eps)
+    return dz.view(z.shape), dg, db
 
 
 # ------------------------------------------------------------------------- layers: forward records
@@ -463,16 +480,23 @@ class _FeatureNetTrain(torch.autograd.Function):
 
 def featurenet_train(fnet, imgs):
     """FeatureNet.forward in train mode for one sample's views imgs [N,3,H,W] -> (stage1, stage2, stage3)
-    NCHW, differentiable w.r.t. fnet's parameters; updates the BatchNorm running statistics per view
-    as the reference's per-view calls do."""
+    NCHW [N,C,h,w], or for a batch imgs [B,N,3,H,W] -> [B,N,C,h,w] each (views of view-major storage);
+    differentiable w.r.t. fnet's parameters; updates the BatchNorm running statistics per view as the
+    reference's per-view calls do (models/TransMVSNet.py:151-153: each call sees that view's B images)."""
     if not imgs.is_cuda:
         raise RuntimeError("featurenet_train runs on the GPU only (no CPU fallback)")
-    if imgs.dim() != 4 or imgs.shape[1] != 3:
-        raise ValueError("featurenet_train: imgs must be [N, 3, H, W] (one sample's views)")
-    tape = _Tape(imgs.shape[0])
+    if imgs.dim() not in (4, 5) or imgs.shape[-3] != 3:
+        raise ValueError("featurenet_train: imgs must be [N, 3, H, W] (one sample's views) or [B, N, 3, H, W]")
+    batch = imgs.shape[0] if imgs.dim() == 5 else None
+    if batch is not None:  # view-major: view v's B images are rows v*B .. v*B + B - 1
+        imgs = imgs.transpose(0, 1).reshape(-1, *imgs.shape[2:])
+    n_views = imgs.shape[0] // (batch or 1)
+    tape = _Tape(n_views)
     params = list(fnet.parameters())
     with torch.cuda.device(imgs.device):
         s1, s2, s3 = _FeatureNetTrain.apply(imgs, fnet, tape, *params)
         # views in order, as the reference's per-view calls (closed form, bn_running.py)
         update_running_stats([(bn, mean, var, n) for bn, (mean, var), n in tape.stats], BN_MOMENTUM)
+    if batch is not None:
+        s1, s2, s3 = (t.view(n_views, batch, *t.shape[1:]).transpose(0, 1) for t in (s1, s2, s3))
     return s1, s2, s3

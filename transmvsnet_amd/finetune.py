@@ -14,8 +14,12 @@ for DTU) as one driver over this package's HIP training step.
 A sample's images are decoded once on the host, uploaded as uint8 and converted on the GPU
 (tmvs_resize_bilinear_u8 at the image's own size: every fraction is 0, so each value is exactly
 float32(u8) / 255); the raw depth map (and DTU's depth_visual PNG) is uploaded once and the depth / mask
-pyramid comes out of one tmvs_gt_pyramid launch. One sample per rank and step (the reference's batch_size 1
-per process). Not built: apex / --sync_bn, tensorboard summaries, DataParallel, --mode profile.
+pyramid comes out of one tmvs_gt_pyramid launch. --batch_size B samples per rank and step (finetune.py runs 1,
+train.py's DTU recipe 2): the training order is cut into batches of B with the remainder dropped (the
+reference's train loader has drop_last=True), evaluation runs batches of B with a smaller last one, and every
+train-mode BatchNorm takes its statistics over the batch (train.forward_train). focal_bld takes B = 1 only.
+Not built: apex / --sync_bn (BatchNorm statistics stay per rank), tensorboard summaries, DataParallel,
+--mode profile.
 """
 from __future__ import annotations
 
@@ -267,15 +271,74 @@ def rank_order(dataset, seed, epoch, shuffle=True, drop_last=False):
     return list(iter(sampler))
 
 
-# ------------------------------------------------------------------ one sample
-def _batch_of_one(sample, device):
-    """The DataLoader's collation at batch_size 1: a leading batch axis on everything the model reads."""
-    return {"imgs": sample["imgs"][None],
-            "proj_matrix": {k: torch.from_numpy(v)[None] for k, v in sample["proj_matrix"].items()},
-            "depth_values": torch.from_numpy(sample["depth_values"])[None].to(device),
-            "depth": {k: v[None] for k, v in sample["depth"].items()},
-            "mask": {k: v[None] for k, v in sample["mask"].items()},
-            "depth_interval": float(sample["depth_interval"])}
+def batches(order, batch_size, drop_last):
+    """`order` cut into consecutive batches of batch_size, as the DataLoader's BatchSampler does: the
+    remainder is dropped (the reference's train loader, drop_last=True) or kept as a smaller last batch
+    (its test loader)."""
+    b = int(batch_size)
+    if b < 1:
+        raise ValueError(f"batch_size must be at least 1, got {batch_size}")
+    order = list(order)
+    out = [order[i:i + b] for i in range(0, len(order), b)]
+    if drop_last and out and len(out[-1]) < b:
+        out.pop()
+    return out
+
+
+def iters_per_epoch(n_samples, batch_size):
+    """Training iterations per epoch of a rank whose share is n_samples: len(loader) with drop_last=True. The
+    LR milestones (parse_lrepochs) and the first iteration after --resume count in these."""
+    return len(batches(range(n_samples), batch_size, True))
+
+
+class BatchLoader:
+    """A Prefetcher over the flattened `batch_list`, yielding each batch as the list of its uploaded samples
+    (decoded per sample on the host threads, uploaded on the consumer's thread). `wait_s`: the consumer's
+    time inside next() for the whole batch."""
+
+    def __init__(self, dataset, batch_list, workers=2):
+        self.batch_list = [list(b) for b in batch_list]
+        self.samples = Prefetcher(dataset, [i for b in self.batch_list for i in b], workers)
+        self.wait_s = 0.0
+
+    def __len__(self):
+        return len(self.batch_list)
+
+    def __iter__(self):
+        it = iter(self.samples)
+        for b in self.batch_list:
+            group, wait = [], 0.0
+            for _ in b:
+                group.append(next(it))
+                wait += self.samples.wait_s
+            self.wait_s = wait
+            yield group
+        it.close()
+
+
+# ------------------------------------------------------------------ one step
+def collate(samples, device):
+    """The DataLoader's collation: a leading batch axis on everything the model reads. `samples`: one
+    sample dict (batch 1) or a list of them, which must agree in their image size and view count."""
+    if isinstance(samples, dict):
+        samples = [samples]
+    first = samples[0]
+    for i, s in enumerate(samples[1:], 1):
+        if s["imgs"].shape != first["imgs"].shape:
+            raise ValueError(f"a batch needs samples of one image size and view count: sample 0 "
+                             f"({first.get('name', '?')}) has imgs {list(first['imgs'].shape)}, sample {i} "
+                             f"({s.get('name', '?')}) {list(s['imgs'].shape)}; use --batch_size 1 or one --crop")
+    if len(samples) == 1:
+        stack, interval = (lambda ts: ts[0][None]), float(first["depth_interval"])
+    else:
+        stack, interval = torch.stack, torch.tensor([float(s["depth_interval"]) for s in samples])
+    return {"imgs": stack([s["imgs"] for s in samples]),
+            "proj_matrix": {k: stack([torch.from_numpy(s["proj_matrix"][k]) for s in samples])
+                            for k in first["proj_matrix"]},
+            "depth_values": stack([torch.from_numpy(s["depth_values"]) for s in samples]).to(device),
+            "depth": {k: stack([s["depth"][k] for s in samples]) for k in first["depth"]},
+            "mask": {k: stack([s["mask"][k] for s in samples]) for k in first["mask"]},
+            "depth_interval": interval}
 
 
 def _loss_outputs(loss_name, outputs, s, dlossw):
@@ -311,12 +374,13 @@ def tensor2float(scalars):
 
 
 def train_sample(model, opt, sample, loss_name, dlossw):
-    """finetune.py:144-195's body for one sample: train-mode forward, loss, the NaN check that skips the step,
-    backward, the gradient all-reduce, the Adam step. Returns the step's scalars as device tensors (averaged
-    onto rank 0 under torch.distributed) and whether the step was applied."""
+    """finetune.py:144-195's body for one batch (`sample`: a sample dict, or a list of them): train-mode
+    forward, loss, the NaN check that skips the step, backward, the gradient all-reduce, the Adam step.
+    Returns the step's scalars as device tensors (averaged onto rank 0 under torch.distributed) and whether
+    the step was applied."""
     model.train()
     opt.zero_grad()
-    s = _batch_of_one(sample, sample["imgs"].device)
+    s = collate(sample, (sample if isinstance(sample, dict) else sample[0])["imgs"].device)
     outputs = model(s["imgs"], s["proj_matrix"], s["depth_values"])
     total, scalars = _loss_outputs(loss_name, outputs, s, dlossw)
     applied = not np.isnan(total.item())
@@ -337,24 +401,31 @@ def train_sample(model, opt, sample, loss_name, dlossw):
 
 @torch.no_grad()
 def test_sample(model, sample, loss_name, dlossw, eval_metrics):
-    """The eval-mode forward, the loss and the metrics of one sample as device tensors (no host sync).
-    eval_metrics (dtu_yao): train.py:216-228's twelve scalars on the stage-3 depth."""
+    """The eval-mode forward, the loss and the metrics of one batch (`sample`: a sample dict, or a list of
+    them) as device tensors (no host sync). eval_metrics (dtu_yao): train.py:216-228's twelve scalars on the
+    stage-3 depth, per image and then averaged over the batch (utils.compute_metrics_for_each_image)."""
     model.eval()
-    s = _batch_of_one(sample, sample["imgs"].device)
+    s = collate(sample, (sample if isinstance(sample, dict) else sample[0])["imgs"].device)
     outputs = model(s["imgs"], s["proj_matrix"], s["depth_values"])
     _, scalars = _loss_outputs(loss_name, outputs, s, dlossw)
     if eval_metrics:
-        m = ops.depth_eval_metrics(outputs["depth"].float().contiguous(), s["depth"]["stage3"], s["mask"]["stage3"])
+        est, gt, mask = outputs["depth"].float().contiguous(), s["depth"]["stage3"], s["mask"]["stage3"]
+        if est.shape[0] == 1:
+            m = ops.depth_eval_metrics(est, gt, mask)
+        else:
+            m = torch.stack([ops.depth_eval_metrics(est[i], gt[i].contiguous(), mask[i].contiguous())
+                             for i in range(est.shape[0])]).mean(0)
         scalars.update({name: m[i] for i, name in enumerate(ops.EVAL_METRIC_NAMES)})
     return scalars
 
 
 def evaluate(model, dataset, args, loss_name, dlossw, verbose=True):
     """finetune.test / the testing half of finetune.train (:98-141): the mean of every scalar over the test
-    set (DictAverageMeter). The per-sample scalars stay on the device; they are summed there and read once."""
+    set (DictAverageMeter): batches of --batch_size with a smaller last one, the mean over the batches. The
+    per-batch scalars stay on the device; they are summed there and read once."""
     import torch.distributed as dist
     order = rank_order(dataset, args.seed, 0, shuffle=False)
-    loader = Prefetcher(dataset, order, args.workers)
+    loader = BatchLoader(dataset, batches(order, getattr(args, "batch_size", 1), False), args.workers)
     names, total, t0 = None, None, time.time()
     for i, sample in enumerate(loader):
         scalars = test_sample(model, sample, loss_name, dlossw, args.dataset == "dtu_yao")
@@ -402,11 +473,13 @@ def _log(logdir, record):
 def train(model, opt, train_set, test_set, start_epoch, args, loss_name, dlossw):
     """finetune.train (:55-125). The learning rate of global iteration len(loader) * epoch + batch is
     warmup_multistep_lr's, set on the optimizer before the step."""
-    iters = len(rank_order(train_set, args.seed, 0, drop_last=True))
+    bsz = getattr(args, "batch_size", 1)
+    iters = iters_per_epoch(len(rank_order(train_set, args.seed, 0, drop_last=True)), bsz)
     milestones, gamma = parse_lrepochs(args.lrepochs, iters)
     main_rank = _rank() == 0
     for epoch in range(start_epoch, args.epochs):
-        loader = Prefetcher(train_set, rank_order(train_set, args.seed, epoch, drop_last=True), args.workers)
+        loader = BatchLoader(train_set, batches(rank_order(train_set, args.seed, epoch, drop_last=True), bsz, True),
+                             args.workers)
         for batch, sample in enumerate(loader):
             t0 = time.perf_counter()
             step = iters * epoch + batch
@@ -434,9 +507,11 @@ def train(model, opt, train_set, test_set, start_epoch, args, loss_name, dlossw)
 # ------------------------------------------------------------------ command line
 def make_parser():
     p = argparse.ArgumentParser(
-        description="Train / fine-tune TransMVSNet on BlendedMVS or DTU scan folders (HIP training step, one "
-                    "sample per rank). Not built: apex (--using_apex, --sync_bn), tensorboard summaries, "
-                    "DataParallel and --mode profile; start one process per GPU with torchrun for DDP.")
+        description="Train / fine-tune TransMVSNet on BlendedMVS or DTU scan folders (HIP training step, "
+                    "--batch_size samples per rank and step with BatchNorm statistics over the batch; "
+                    "--loss focal_bld takes --batch_size 1 only). Not built: apex (--using_apex, --sync_bn: "
+                    "BatchNorm statistics stay per rank), tensorboard summaries, DataParallel and --mode "
+                    "profile; start one process per GPU with torchrun for DDP.")
     p.add_argument("--mode", default="train", choices=["train", "test"], help="train or test")
     p.add_argument("--dataset", default="dtu_yao", choices=sorted(DATASETS), help="select dataset")
     p.add_argument("--trainpath", help="train datapath")
@@ -448,7 +523,8 @@ def make_parser():
     p.add_argument("--lrepochs", type=str, default="10,12,14:2", help="epoch ids to downscale lr and the downscale rate")
     p.add_argument("--wd", type=float, default=0.0001, help="weight decay")
     p.add_argument("--nviews", type=int, default=5, help="total number of views")
-    p.add_argument("--batch_size", type=int, default=1, choices=[1], help="samples per rank and step (1)")
+    p.add_argument("--batch_size", type=int, default=1,
+                   help="samples per rank and step (train.py's DTU recipe: 2; focal_bld: 1 only)")
     p.add_argument("--numdepth", type=int, default=192, help="the number of depth values")
     p.add_argument("--interval_scale", type=float, default=1.06, help="the depth interval scale (dtu_yao)")
     p.add_argument("--loadckpt", default=None, help="load a specific checkpoint ('model' only, strict)")
@@ -479,6 +555,11 @@ def parse_args(argv=None):
         parser.error("--resume needs --mode train")
     if args.resume and args.loadckpt is not None:
         parser.error("--resume and --loadckpt exclude each other")
+    if args.batch_size < 1:
+        parser.error(f"--batch_size must be at least 1, got {args.batch_size}")
+    if args.batch_size > 1 and resolve_loss(args)[0] == "focal_bld":
+        from .loss import FOCAL_BLD_BATCH_MSG
+        parser.error(f"--batch_size {args.batch_size} with --loss focal_bld: {FOCAL_BLD_BATCH_MSG}")
     if args.testpath is None:
         args.testpath = args.trainpath
     return args

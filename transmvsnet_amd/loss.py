@@ -16,6 +16,11 @@ import torch
 from . import ops
 
 ENTROPY_WEIGHT = 2.0  # module.py:542 / :566
+# finetune.py:159's focal_loss_bld divides [B,H,W] errors by the [B] depth_interval, which broadcasts along W
+# (module.py:561-592): the reference itself cannot run it on a batch of more than one sample
+FOCAL_BLD_BATCH_MSG = ("focal_bld takes one sample per step: BlendedMVS fine-tuning is batch 1 in the reference "
+                       "(finetune.py, BATCH_SIZE=1; its focal_loss_bld cannot scale a batch by per-sample depth "
+                       "intervals). A batch of more than one is for the loss trans_mvsnet, the dtu_yao default")
 
 
 def _f32(t):
@@ -109,7 +114,8 @@ def focal_loss_bld(inputs, depth_gt_ms, mask_ms, depth_interval, dlossw=None, re
     than one element is refused here rather than silently reduced to sample 0's."""
     if torch.is_tensor(depth_interval) and depth_interval.numel() != 1:
         raise ValueError(f"focal_loss_bld: depth_interval must be a number or a one-element tensor, got shape "
-                         f"{tuple(depth_interval.shape)} (the reference's [B] broadcast is along W)")
+                         f"{tuple(depth_interval.shape)} (the reference's [B] broadcast is along W). "
+                         + FOCAL_BLD_BATCH_MSG)
     total, depth_loss, _, _, grads = _stage_losses(inputs, depth_gt_ms, mask_ms, dlossw, return_grad)
     di = float(depth_interval.reshape(-1)[0]) if torch.is_tensor(depth_interval) else float(depth_interval)
     m = ops.depth_metrics(_f32(inputs["stage3"]["depth"]), _f32(depth_gt_ms["stage3"]), _f32(mask_ms["stage3"]), di)

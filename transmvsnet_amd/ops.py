@@ -1051,6 +1051,49 @@ def pixelwise_train_backward(sims, pwp, stats, view_w, dstar, dview_w, dsims):
     return dpwp
 
 
+def _pw_sims_batched(op, sims):
+    _dev(sims, "sims")
+    if sims.dim() != 5:
+        raise ValueError(f"{op}: sims must be [B, V, D, H, W], not {list(sims.shape)}")
+    return sims.shape
+
+
+def pixelwise_train_forward_batched(sims, pwp):
+    """tmvs_pixelwise_train_forward_batched: sims [B,V,D,H,W], pwp [201] -> (stats [V,48] joint over each view's
+    B*D*H*W elements, view_w [B,V,H,W], dstar int32 [B,V,H,W])."""
+    op = "pixelwise_train_forward_batched"
+    b, v, d, h, w = _pw_sims_batched(op, sims)
+    _pw_shaped(op, pwp, "pwp", (_lib.PW_NPARAMS,), sims)
+    ws = torch.empty(_lib_h().tmvs_pixelwise_train_workspace() // 4 + 64, device=sims.device)
+    stats = torch.empty(v, 48, device=sims.device)
+    vw = torch.empty(b, v, h, w, device=sims.device)
+    dstar = torch.empty(b, v, h, w, device=sims.device, dtype=torch.int32)
+    with _Span("tmvs_pixelwise_train_forward_batched"):
+        _lib.check(_lib_h().tmvs_pixelwise_train_forward_batched(_ptr(sims), b, v, d, h, w, _ptr(pwp), _ptr(ws),
+                                                                 ws.numel() * 4, _ptr(stats), _ptr(vw), _ptr(dstar),
+                                                                 _stream()), "tmvs_pixelwise_train_forward_batched")
+    return stats, vw, dstar
+
+
+def pixelwise_train_backward_batched(sims, pwp, stats, view_w, dstar, dview_w, dsims):
+    """tmvs_pixelwise_train_backward_batched: sims / dsims [B,V,D,H,W], stats [V,48], view_w / dstar / dview_w
+    [B,V,H,W]; adds the PixelwiseNet path into dsims (in place) -> dpwp [201]."""
+    op = "pixelwise_train_backward_batched"
+    b, v, d, h, w = _pw_sims_batched(op, sims)
+    for t, n, shape in ((pwp, "pwp", (_lib.PW_NPARAMS,)), (stats, "stats", (v, 48)), (view_w, "view_w", (b, v, h, w)),
+                        (dview_w, "dview_w", (b, v, h, w)), (dsims, "dsims", (b, v, d, h, w))):
+        _pw_shaped(op, t, n, shape, sims)
+    _pw_shaped(op, dstar, "dstar", (b, v, h, w), sims, torch.int32)
+    ws = torch.empty(_lib_h().tmvs_pixelwise_train_workspace() // 4 + 64, device=sims.device)
+    dpwp = torch.zeros(_lib.PW_NPARAMS, device=sims.device)
+    with _Span("tmvs_pixelwise_train_backward_batched"):
+        _lib.check(_lib_h().tmvs_pixelwise_train_backward_batched(_ptr(sims), b, v, d, h, w, _ptr(pwp), _ptr(stats),
+                                                                  _ptr(view_w), _ptr(dstar), _ptr(dview_w), _ptr(ws),
+                                                                  ws.numel() * 4, _ptr(dsims), _ptr(dpwp), _stream()),
+                   "tmvs_pixelwise_train_backward_batched")
+    return dpwp
+
+
 def upsample2_add_nhwc(r, lateral_nchw):
     """tmvs_upsample2_add_nhwc: r [N,h,w,C] -> bilinear x2 + lateral [N,C,2h,2w] -> [N,2h,2w,C]."""
     _dev(r, "r")
@@ -1255,6 +1298,7 @@ def adam_step_dev(param_flat, grad_flat, exp_avg, exp_avg_sq, lr, betas, eps, we
 for _name in ("conv3d_generic", "conv3d_mfma", "conv3d_wgrad", "bn_stats", "bn_relu_train", "bn_relu_backward", "bn_stats_grouped", "bn_relu_train_grouped",
               "bn_relu_backward_grouped", "warp_corr_backward",
               "upsample2_add_nhwc", "upsample2_backward_nhwc", "pixelwise_train_forward", "aggregate_train", "aggregate_train_backward", "pixelwise_train_backward",
+              "pixelwise_train_forward_batched", "pixelwise_train_backward_batched",
               "token_linear", "token_wgrad", "layer_norm_fwd", "layer_norm_bwd", "linattn_fwd", "linattn_bwd_q",
               "linattn_bwd_kv", "adam_step", "adam_step_dev"):
     globals()[_name] = _on_tensor_device(globals()[_name])

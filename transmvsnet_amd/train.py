@@ -193,10 +193,19 @@ class _PathwayStep(torch.autograd.Function):
 def pathway_train(model, stage1_nhwc, stage2_nchw, stage3_nchw):
     """FMT_with_pathway's stage-2/3 features (models/FMT.py:221-228) from the FMT output stage1_nhwc
     [N,h1,w1,32] and FeatureNet's stage2 [N,16,2h1,2w1] / stage3 [N,8,4h1,4w1] (NCHW), differentiable
-    w.r.t. all three and the four conv weights -> (stage2 [N,2h1,2w1,16], stage3 [N,4h1,4w1,8]) NHWC."""
+    w.r.t. all three and the four conv weights -> (stage2 [N,2h1,2w1,16], stage3 [N,4h1,4w1,8]) NHWC.
+    With a leading batch ([B,N,...] each) the outputs carry it too: the steps are convolutions and an
+    interpolation per image (no BatchNorm), so the B*N images go through one call, and the weight
+    gradients are sums over all of them."""
     fp = model.FMT_with_pathway
+    lead = stage1_nhwc.shape[:-3]
+    if len(lead) == 2:
+        stage1_nhwc, stage2_nchw, stage3_nchw = (t.reshape(-1, *t.shape[2:])
+                                                 for t in (stage1_nhwc, stage2_nchw, stage3_nchw))
     st2 = _PathwayStep.apply(stage1_nhwc, stage2_nchw, fp.dim_reduction_1.weight, fp.smooth_1.weight)
     st3 = _PathwayStep.apply(st2, stage3_nchw, fp.dim_reduction_2.weight, fp.smooth_2.weight)
+    if len(lead) == 2:
+        st2, st3 = st2.view(*lead, *st2.shape[1:]), st3.view(*lead, *st3.shape[1:])
     return st2, st3
 
 
@@ -315,9 +324,13 @@ def fmt_params(model):
 def fmt_train(model, stage1_nchw):
     """FMT_with_pathway's FMT part (models/FMT.py:212-220) for training: FeatureNet stage-1 features
     [nv,32,h,w] (reference view first) -> FMT output [nv,h,w,32] NHWC, differentiable w.r.t. the input
-    and every FMT parameter (HIP forward and backward)."""
+    and every FMT parameter (HIP forward and backward). [B,nv,32,h,w] -> [B,nv,h,w,32]: attention is per
+    sample and view (models/FMT.py:136-228 has no BatchNorm), so the token kernels run sample by sample
+    and autograd adds the parameter gradients over the samples."""
     if not stage1_nchw.is_cuda:
         raise RuntimeError("fmt_train runs on the GPU only (no CPU fallback)")
+    if stage1_nchw.dim() == 5:
+        return torch.stack([fmt_train(model, s) for s in stage1_nchw])
     nv, c, h, w = stage1_nchw.shape
     if nv < 2 or c != 32:
         raise ValueError("fmt_train: stage1 must be [nv >= 2, 32, h, w]")
@@ -521,35 +534,50 @@ def costregnet_train(module, x):
 
 class _AggregateTrain(torch.autograd.Function):
     """View aggregation (TransMVSNet.py:71-93) with, at stage 1, the train-mode PixelwiseNet weights
-    (TransMVSNet.py:10-30), forward and backward on csrc/pw_train.hip. Outputs (sim [D,H,W], the
-    view weights used [V,H',W'], non-differentiable as the reference returns them detached)."""
+    (TransMVSNet.py:10-30), forward and backward on csrc/pw_train.hip. sims [V,D,H,W] (one sample) or
+    [B,V,D,H,W]: the PixelwiseNet's BatchNorm statistics are joint over a view's B volumes (one batched
+    call; the reference calls it per view on [B,1,D,h,w]), the aggregation has no coupling between samples
+    and runs per sample. Outputs (sim [(B,)D,H,W], the view weights used [(B,)V,H',W'], non-differentiable
+    as the reference returns them detached)."""
 
     @staticmethod
     def forward(ctx, sims, pwp, vw_given, vw_shift, stats_out):
         sims = sims.contiguous()
+        single = sims.dim() == 4
+        sb = sims[None] if single else sims
+        b, v, d, h, w = sb.shape
         if vw_given is None:
-            stats, vw, dstar = ops.pixelwise_train_forward(sims, pwp.detach().contiguous())
+            stats, vw, dstar = ops.pixelwise_train_forward_batched(sb, pwp.detach().contiguous())
             stats_out.append(stats)
             ctx.pw = (stats, dstar)
         else:
             vw = vw_given.contiguous()
+            vw = vw[None] if single else vw
             ctx.pw = None
-        sim, wsum = ops.aggregate_train(sims, vw, vw_shift)
-        ctx.vw_shift = vw_shift
-        ctx.save_for_backward(sims, sim, wsum, vw, pwp)
-        ctx.mark_non_differentiable(vw)
-        return sim, vw
+        sim = torch.empty(b, d, h, w, device=sims.device)
+        wsums = [ops.aggregate_train(sb[i], vw[i], vw_shift, sim=sim[i])[1] for i in range(b)]
+        ctx.vw_shift, ctx.single = vw_shift, single
+        ctx.save_for_backward(sb, sim, vw, pwp, *wsums)
+        sim_out, vw_out = (sim[0], vw[0]) if single else (sim, vw)
+        ctx.mark_non_differentiable(vw_out)
+        return sim_out, vw_out
 
     @staticmethod
     def backward(ctx, dsim, _dvw):
-        sims, sim, wsum, vw, pwp = ctx.saved_tensors
+        sb, sim, vw, pwp, *wsums = ctx.saved_tensors
         stage1 = ctx.pw is not None
-        dsims, dvw = ops.aggregate_train_backward(dsim.contiguous(), sims, sim, wsum, vw, ctx.vw_shift, stage1)
+        b, v, d, h, w = sb.shape
+        dsim = dsim.contiguous().view(b, d, h, w)
+        dsims = torch.empty_like(sb)
+        dvw = torch.empty(b, v, h, w, device=sb.device) if stage1 else None
+        for i in range(b):
+            ops.aggregate_train_backward(dsim[i], sb[i], sim[i], wsums[i], vw[i], ctx.vw_shift, stage1, dsims=dsims[i],
+                                         dview_w=dvw[i] if stage1 else None)
         dpwp = None
         if stage1:
             stats, dstar = ctx.pw
-            dpwp = ops.pixelwise_train_backward(sims, pwp.detach().contiguous(), stats, vw, dstar, dvw, dsims)
-        return dsims, dpwp, None, None, None
+            dpwp = ops.pixelwise_train_backward_batched(sb, pwp.detach().contiguous(), stats, vw, dstar, dvw, dsims)
+        return (dsims[0] if ctx.single else dsims), dpwp, None, None, None
 
 
 def _pw_params(pw):
@@ -562,13 +590,18 @@ def _pw_params(pw):
 def aggregate_train(sims, model, vw_given=None, vw_shift=0):
     """DepthNet's view aggregation for training; at stage 1 (vw_given None) the view weights come
     from PixelwiseNet in train mode, whose BatchNorm running statistics are updated once per view
-    (the reference calls it per view). Returns (sim [D,H,W], view weights)."""
+    (the reference calls it per view). sims [V,D,H,W] -> (sim [D,H,W], view weights [V,H',W']); a batch
+    sims [B,V,D,H,W] -> (sim [B,D,H,W], view weights [B,V,H',W']) with the PixelwiseNet statistics, and the
+    n of the unbiased running variance, over the B*D*H*W elements of each view (TransMVSNet.py:71-77 runs
+    it on [B,1,D,h,w])."""
     pw = model.DepthNet.pixel_wise_net
+    if sims.dim() not in (4, 5):
+        raise ValueError(f"aggregate_train: sims must be [V,D,H,W] or [B,V,D,H,W], not {list(sims.shape)}")
     stats = []
     sim, vw = _AggregateTrain.apply(sims, _pw_params(pw), vw_given, vw_shift, stats)
     if stats:
-        n = sims.shape[1] * sims.shape[2] * sims.shape[3]
-        st = torch.stack(list(stats[0]))  # [views, 48], views in order
+        n = sims.numel() // sims.shape[-4]  # elements per view: (B *) D * H * W
+        st = stats[0]  # [views, 48], views in order
         update_running_stats([(pw.conv0.bn, st[:, 0:16], st[:, 16:32], n), (pw.conv1.bn, st[:, 32:40], st[:, 40:48], n)],
                              pw.conv0.bn.momentum)
     return sim, vw
@@ -596,34 +629,43 @@ class _SoftmaxWTA(torch.autograd.Function):
 
 
 def depth_stages_forward_train(model, stage_features, proj_matrix, depth_values, img_hw):
-    """The three DepthNet stages of a training forward for ONE sample (B = 1): TransMVSNet.forward's
+    """The three DepthNet stages of a training forward for a batch of B >= 1 samples: TransMVSNet.forward's
     stage loop (models/TransMVSNet.py:168-221) in train mode, returning its output dict (per stage
     depth / photo_confidence / prob_volume / depth_values, plus the stage-3 keys at the top level).
     prob_volume is differentiable (through the HIP softmax, CostRegNet, aggregation / PixelwiseNet
     and cost-volume backward into the stage features); each prob_volume also carries its logits as
     `_tmvs_logits`, so transmvsnet_amd.loss can seed the backward with d loss / d logits directly.
 
-    stage_features: {stage: [N, h, w, C]} NHWC FMT/pathway outputs, reference view first; proj_matrix
-    {stage: [1, N, 2, 4, 4]}; depth_values [1, 192]. The CostRegNets and the PixelwiseNet run in
-    train mode (their BatchNorm running statistics are updated)."""
+    stage_features: {stage: [N, h, w, C]} (one sample) or {stage: [B, N, h, w, C]} NHWC FMT/pathway
+    outputs, reference view first; proj_matrix {stage: [B, N, 2, 4, 4]}; depth_values [B, 192]. The
+    CostRegNets and the PixelwiseNet run in train mode (their BatchNorm running statistics are updated),
+    with batch statistics over the whole batch as in the reference: hypotheses, warp + correlation, the
+    view aggregation and softmax / WTA are per sample (cameras and depth ranges differ per sample), the
+    PixelwiseNet takes its statistics per view over B*D*h*w and the CostRegNets over B*D*h*w."""
     from .model import STAGE_SCALES
     dev = stage_features["stage1"].device
+    b = 1 if stage_features["stage1"].dim() == 4 else stage_features["stage1"].shape[0]
+    if depth_values.shape[0] != b or any(proj_matrix[f"stage{s + 1}"].shape[0] != b for s in range(3)):
+        raise ValueError(f"depth_stages_forward_train: {b} sample(s) of features, but depth_values "
+                         f"{list(depth_values.shape)} and proj_matrix {list(proj_matrix['stage1'].shape)}")
     with torch.cuda.device(dev):
         dv = depth_values.to(dev, torch.float32).contiguous()
         outputs, prev_raw, vw_det = {}, None, None
         for s in range(3):
             name = f"stage{s + 1}"
             f = stage_features[name]
+            f = f[None] if f.dim() == 4 else f
             hyp = ops.stage_hypotheses(dv, prev_raw, model.ndepths[s], model.depth_interals_ratio[s], img_hw,
                                        STAGE_SCALES[s])
-            rows = ops.proj_rows(proj_matrix[name])[0]
-            sims = warp_corr_views(f[0], f[1:], hyp[0], rows, rot_order=model.warp_rot_order,
-                                   planes=prev_raw is None)  # [V,D,h,w]; stage 1: depth planes
+            rows = ops.proj_rows(proj_matrix[name])
+            sims = [warp_corr_views(f[i, 0], f[i, 1:], hyp[i], rows[i], rot_order=model.warp_rot_order,
+                                    planes=prev_raw is None) for i in range(b)]  # [V,D,h,w]; stage 1: depth planes
+            sims = sims[0] if b == 1 else torch.stack(sims)
             if s == 0:  # TransMVSNet.py:107 returns the stage-1 view weights detached
                 sim, vw_det = aggregate_train(sims, model)
             else:       # nearest x2 per stage (:194) = reading the stage-1 map at (y >> s, x >> s)
                 sim, _ = aggregate_train(sims, model, vw_det, s)
-            logits = costregnet_train(model.cost_regularization[s].train(), sim.unsqueeze(0))
+            logits = costregnet_train(model.cost_regularization[s].train(), sim.unsqueeze(0) if b == 1 else sim)
             prob, depth, raw, conf = _SoftmaxWTA.apply(logits, hyp)
             prob._tmvs_logits = logits
             outputs[name] = {"depth": depth, "photo_confidence": conf, "prob_volume": prob, "depth_values": hyp}
@@ -634,11 +676,13 @@ def depth_stages_forward_train(model, stage_features, proj_matrix, depth_values,
 
 def depth_stages_train(model, stage_features, proj_matrix, depth_values, depth_gt_ms, mask_ms, img_hw,
                        dlossw=(0.5, 1.0, 2.0), loss="trans_mvsnet", depth_interval=None):
-    """One training step's DepthNet stages for ONE sample (B = 1), forward and backward.
+    """One training step's DepthNet stages for a batch of B >= 1 samples, forward and backward.
 
-    stage_features: {stage: [N, h, w, C]} NHWC FMT/pathway outputs, reference view first (leaf tensors
-    that require grad collect d loss / d features); proj_matrix {stage: [1, N, 2, 4, 4]}; depth_values
-    [1, 192]; depth_gt_ms / mask_ms {stage: [1, h, w]}. The CostRegNets and the PixelwiseNet run in train
+    stage_features: {stage: [N, h, w, C]} (B = 1) or {stage: [B, N, h, w, C]} NHWC FMT/pathway outputs,
+    reference view first (leaf tensors that require grad collect d loss / d features); proj_matrix {stage:
+    [B, N, 2, 4, 4]}; depth_values [B, 192]; depth_gt_ms / mask_ms {stage: [B, h, w]}. The loss is the mean
+    over the batch of the per-sample masked means (models/module.py:495-558; focal_bld takes B = 1 only, as
+    in the reference, whose BlendedMVS fine-tuning runs batch 1). The CostRegNets and the PixelwiseNet run in train
     mode (their BatchNorm running statistics are updated). Calls backward of the loss and returns
     (total_loss, outputs) with outputs as TransMVSNet.forward's stage dicts. loss="trans_mvsnet":
     train.py:152's trans_mvsnet_loss (dlossw default 0.5,1,2); loss="focal_bld": finetune.py:159's
@@ -650,6 +694,8 @@ def depth_stages_train(model, stage_features, proj_matrix, depth_values, depth_g
     if loss == "focal_bld" and depth_interval is None:
         raise ValueError("depth_stages_train: focal_bld needs depth_interval")
     from . import loss as loss_mod
+    if loss == "focal_bld" and depth_values.shape[0] != 1:
+        raise ValueError("depth_stages_train: " + loss_mod.FOCAL_BLD_BATCH_MSG)
     dev = stage_features["stage1"].device
     with torch.cuda.device(dev):
         outputs = depth_stages_forward_train(model, stage_features, proj_matrix, depth_values, img_hw)
@@ -682,16 +728,20 @@ def forward_train(model, imgs, proj_matrix, depth_values):
     three DepthNet stages (depth_stages_forward_train), every block differentiable through its HIP
     backward, so the reference's train_sample body (finetune.py:144-168) runs unchanged:
     ``model.train(); outputs = model(imgs, proj, dv); loss = focal_loss_bld(outputs, ...)[0];
-    loss.backward(); optimizer.step()``. One sample per call (B = 1: C5's DDP runs one sample per
-    rank, finetune.py batch_size 1 per process)."""
+    loss.backward(); optimizer.step()``. imgs [B, N, 3, H, W] with any B >= 1 (train.py's DTU recipe runs
+    BATCH_SIZE=2 per GPU, finetune.py's 1): every train-mode BatchNorm takes its statistics over the whole
+    batch as the reference's does -- FeatureNet's per view over B*h*w (models/TransMVSNet.py:151-153),
+    PixelwiseNet's per view over B*D*h*w (:71-77), the CostRegNets' over B*D*h*w -- and everything else is
+    per sample. B = 1 runs the single-sample code as before."""
     from .featurenet_train import featurenet_train
-    if imgs.dim() != 5 or imgs.shape[0] != 1:
-        raise ValueError("TransMVSNet train-mode forward takes one sample per call: imgs [1, N, 3, H, W]")
+    if imgs.dim() != 5 or imgs.shape[0] < 1 or imgs.shape[1] < 2:
+        raise ValueError(f"TransMVSNet train-mode forward: imgs must be [B >= 1, N >= 2, 3, H, W], not "
+                         f"{list(imgs.shape)}")
     if not imgs.is_cuda:
         raise RuntimeError("TransMVSNet (HIP) needs GPU inputs; the HIP path has no CPU fallback")
     h, w = imgs.shape[3], imgs.shape[4]
     with torch.cuda.device(imgs.device):
-        s1, s2, s3 = featurenet_train(model.feature, imgs[0])
+        s1, s2, s3 = featurenet_train(model.feature, imgs[0] if imgs.shape[0] == 1 else imgs)
         st1 = fmt_train(model, s1)
         st2, st3 = pathway_train(model, st1, s2, s3)
         return depth_stages_forward_train(model, {"stage1": st1, "stage2": st2, "stage3": st3}, proj_matrix,
