@@ -859,8 +859,9 @@ def test_training_host_logic():
 
 
 def test_every_launching_op_is_device_guarded():
-    """Every public op in ops.py that launches on the current stream (_stream()) runs under the
-    device guard of its first GPU tensor argument (costregnet_wta was missing)."""
+    """Every public op in ops.py that launches on the current stream (through _launch(, which the shared
+    bodies' names *_launch( end in too, or _stream() itself) runs under the device guard of its first GPU
+    tensor argument (costregnet_wta was missing)."""
     import inspect
 
     from transmvsnet_amd import ops
@@ -869,7 +870,7 @@ def test_every_launching_op_is_device_guarded():
         if name.startswith("_") or not inspect.isfunction(fn) or fn.__module__ != ops.__name__:
             continue
         src = inspect.getsource(inspect.unwrap(fn))
-        if "_stream()" in src and not getattr(fn, "device_guarded", False):
+        if ("_launch(" in src or "_stream()" in src) and not getattr(fn, "device_guarded", False):
             missing.append(name)
     assert not missing, missing
 

@@ -29,7 +29,7 @@ import torch
 
 from . import data, ops
 from ._lib import (DYNFUSE_FINAL, DYNFUSE_GEO, DYNFUSE_MAX_SRC, DYNFUSE_PAIR_FLOATS, DYNFUSE_PHOTO,
-                   DYNFUSE_REF_FLOATS, check, load)
+                   DYNFUSE_REF_FLOATS)
 
 
 # ------------------------------------------------------------------ host-side matrices
@@ -106,7 +106,6 @@ def filter_view(depths, confidence, Ks, Es, ref, srcs, photo_threshold=0.3, thre
             raise RuntimeError(f"filter_view: {name} must be contiguous float32")
     if depths.dim() != 3 or confidence.shape != depths.shape[1:]:
         raise ValueError("filter_view: depths must be [V, H, W] and confidence [H, W]")
-    lib = load()
     v, h, w = depths.shape
     srcs = _check_views(v, ref, srcs)
     if int(thres_view) < 1 or subpixel_bits not in (0, 5):
@@ -116,13 +115,9 @@ def filter_view(depths, confidence, Ks, Es, ref, srcs, photo_threshold=0.3, thre
         raise ValueError("filter_view: consts do not match srcs")
     if out is None:
         out = alloc_outputs(h, w, depths.device)
-    with ops._Span("tmvs_dynamic_fusion"):
-        check(lib.tmvs_dynamic_fusion(depths.data_ptr(), v, h, w, int(ref), idx.data_ptr(), len(srcs),
-                                      pairs.data_ptr(), rblk.data_ptr(), confidence.data_ptr(),
-                                      float(photo_threshold), int(thres_view), int(subpixel_bits),
-                                      out["geo_count"].data_ptr(), out["mask"].data_ptr(),
-                                      out["depth_avg"].data_ptr(), out["xyz"].data_ptr(), ops._stream()),
-              "tmvs_dynamic_fusion")
+    ops._launch("tmvs_dynamic_fusion", depths, v, h, w, int(ref), idx, len(srcs), pairs, rblk, confidence,
+                float(photo_threshold), int(thres_view), int(subpixel_bits), out["geo_count"], out["mask"],
+                out["depth_avg"], out["xyz"])
     m = out["mask"]
     return {"geo_count": out["geo_count"], "photo": (m & DYNFUSE_PHOTO) != 0, "geo": (m & DYNFUSE_GEO) != 0,
             "final": (m & DYNFUSE_FINAL) != 0, "depth_avg": out["depth_avg"], "xyz": out["xyz"], "mask": m}

@@ -15,7 +15,6 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import check, load
 
 CAM_FLOATS = 32  # csrc/fusion.hip fz::CAM: P[12], RK_inv[9], C4[3], fx, pad
 
@@ -110,7 +109,6 @@ def fuse(rgbd, cams_packed, consistent_threshold=3, depth_threshold=0.25):
 
     rgbd: [V, H, W, 4] float32 (device tensor or array); cams_packed: [V, 32] (camera_params).
     Returns (coords [N, 3], textures [N, 3]) as device tensors."""
-    lib = load()
     if not isinstance(rgbd, torch.Tensor) or not rgbd.is_cuda:
         raise RuntimeError("fuse: rgbd must be a CUDA tensor (HIP kernel; no CPU fallback)")
     rgbd = rgbd.contiguous().float()
@@ -122,10 +120,8 @@ def fuse(rgbd, cams_packed, consistent_threshold=3, depth_threshold=0.25):
     tex = torch.zeros(h, w, 4, device=rgbd.device)
     xs, ts = [], []
     for ref in range(v):
-        with ops._Span("tmvs_fusibile"):
-            check(lib.tmvs_fusibile(rgbd.data_ptr(), cams.data_ptr(), v, h, w, ref, int(consistent_threshold),
-                                    float(depth_threshold), coord.data_ptr(), tex.data_ptr(), ops._stream()),
-                  "tmvs_fusibile")
+        ops._launch("tmvs_fusibile", rgbd, cams, v, h, w, ref, int(consistent_threshold), float(depth_threshold), coord,
+                    tex)
         keep = (coord[..., 0] != 0) & (coord[..., 1] != 0) & (coord[..., 2] != 0)
         xs.append(coord[..., :3][keep])
         ts.append(tex[..., :3][keep])

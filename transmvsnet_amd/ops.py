@@ -8,6 +8,7 @@ reference does it so the warp coordinates match bit for bit.
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -27,22 +28,29 @@ def set_timer(timer):
     _TIMER = timer
 
 
-class _Span:
-    __slots__ = ("tok",)
+def _call(name, *args, span=None):
+    """One C-ABI call, status checked: tensors go as their data_ptr(), None as NULL and the rest as ctypes
+    converts it by the entry's argtypes (_lib.SIGNATURES). The timer span (`span`, else the entry's name)
+    brackets the library call alone."""
+    fn = getattr(_lib_h(), name)
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    tok = _TIMER.begin(span or name) if _TIMER is not None else None
+    try:
+        _lib.check(fn(*args), name)
+    finally:
+        if tok is not None:
+            _TIMER.end(tok)
 
-    def __init__(self, name):
-        self.tok = _TIMER.begin(name) if _TIMER is not None else None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        if self.tok is not None:
-            _TIMER.end(self.tok)
+def _launch(name, *args, span=None):
+    """_call with the current stream as the entry's last argument."""
+    _call(name, *args, _stream(), span=span)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+def _workspace(query, *dims, device):
+    """(scratch tensor, its size in bytes) for one launch, from the entry's size query `query`(*dims)."""
+    ws = torch.empty(getattr(_lib_h(), query)(*dims) // 4 + 64, device=device)
+    return ws, ws.numel() * 4
 
 
 def _stream():
@@ -55,8 +63,6 @@ def _on_tensor_device(fn):
     """Run `fn` with the current device = the device of its first GPU tensor argument, so its kernels
     launch on that device and on that device's current stream (a model on cuda:1 works without
     torch.cuda.set_device(1))."""
-    import functools
-
     @functools.wraps(fn)
     def wrapped(*args, **kwargs):
         for a in (*args, *kwargs.values()):
@@ -88,9 +94,8 @@ def bn_fold(gamma, beta, mean, var, eps=1e-5):
     v = np.ascontiguousarray(var.detach().cpu().numpy(), np.float32)
     a = np.empty_like(g)
     s = np.empty_like(g)
-    with _Span("tmvs_bn_fold"):
-        _lib.check(_lib_h().tmvs_bn_fold(g.ctypes.data, b.ctypes.data, m.ctypes.data, v.ctypes.data, g.size,
-                                         ctypes.c_float(eps), a.ctypes.data, s.ctypes.data), "tmvs_bn_fold")
+    _call("tmvs_bn_fold", g.ctypes.data, b.ctypes.data, m.ctypes.data, v.ctypes.data, g.size, eps, a.ctypes.data,
+          s.ctypes.data)
     return a, s
 
 
@@ -153,6 +158,7 @@ def warp_flags(rot_order, n_pixels):
 
 
 # ----------------------------------------------------------------- ops
+@_on_tensor_device
 def stage_hypotheses(depth_values, prev_depth, ndepth, ratio, full_hw, stage_scale):
     """Stage glue (models/TransMVSNet.py:174-204): -> [B, D, H/s, W/s]."""
     _dev(depth_values, "depth_values")
@@ -161,13 +167,12 @@ def stage_hypotheses(depth_values, prev_depth, ndepth, ratio, full_hw, stage_sca
     h, w = full_hw
     out = torch.empty(b, ndepth, h // stage_scale, w // stage_scale, device=depth_values.device)
     ph, pw = (prev_depth.shape[1], prev_depth.shape[2]) if prev_depth is not None else (0, 0)
-    with _Span("tmvs_stage_hypotheses"):
-        _lib.check(_lib_h().tmvs_stage_hypotheses(_ptr(depth_values), depth_values.shape[1], _ptr(prev_depth), ph, pw, b,
-                                                  ndepth, ctypes.c_float(ratio), h, w, stage_scale, _ptr(out), _stream()),
-                   "tmvs_stage_hypotheses")
+    _launch("tmvs_stage_hypotheses", depth_values, depth_values.shape[1], prev_depth, ph, pw, b, ndepth, ratio, h, w,
+            stage_scale, out)
     return out
 
 
+@_on_tensor_device
 def warp_corr(ref_nhwc, src_nhwc, proj12, hyp, view_w_in=None, vw_shift=0, vw_offset=0, vw_total=None,
               pw_params=None, partial=False, view_w_out=None, sim_out=None, wsum_out=None, rot_order="auto"):
     """Fused cost volume (models/TransMVSNet.py:58-93). ref [B,H,W,C], src [B,V,H,W,C], proj12 HOST [B,V,12].
@@ -195,25 +200,22 @@ def warp_corr(ref_nhwc, src_nhwc, proj12, hyp, view_w_in=None, vw_shift=0, vw_of
         pw_ptr = pw.ctypes.data
     else:
         pw_ptr = None
-    with _Span("tmvs_warp_corr"):
-        _lib.check(_lib_h().tmvs_warp_corr(_ptr(ref_nhwc), _ptr(src_nhwc), proj.ctypes.data, _ptr(hyp), _ptr(view_w_in),
-                                           vw_shift, vw_offset, vw_total, pw_ptr, b, v, c, d, h, w,
-                                           (_lib.WARP_PARTIAL if partial else 0) | warp_flags(rot_order, h * w),
-                                           _ptr(sim), _ptr(wsum),
-                                           _ptr(view_w_out if view_w_in is None else None), _stream()), "tmvs_warp_corr")
+    _launch("tmvs_warp_corr", ref_nhwc, src_nhwc, proj.ctypes.data, hyp, view_w_in, vw_shift, vw_offset, vw_total,
+            pw_ptr, b, v, c, d, h, w, (_lib.WARP_PARTIAL if partial else 0) | warp_flags(rot_order, h * w), sim, wsum,
+            view_w_out if view_w_in is None else None)
     return sim, wsum, (view_w_out if view_w_in is None else None)
 
 
+@_on_tensor_device
 def aggregate_finalize(sim_sum, w_sum):
     _dev(sim_sum, "sim_sum")
     _dev(w_sum, "w_sum")
     b, d, h, w = sim_sum.shape
-    with _Span("tmvs_aggregate_finalize"):
-        _lib.check(_lib_h().tmvs_aggregate_finalize(_ptr(sim_sum), _ptr(w_sum), b, d, h, w, _stream()),
-                   "tmvs_aggregate_finalize")
+    _launch("tmvs_aggregate_finalize", sim_sum, w_sum, b, d, h, w)
     return sim_sum
 
 
+@_on_tensor_device
 def homo_warping(src_fea, src_proj, ref_proj, depth_values, rot_order="auto"):
     """Seam-compatible homo_warping (models/module.py:284-322): [B,C,H,W] -> [B,C,D,H,W]."""
     _dev(src_fea, "src_fea")
@@ -223,13 +225,12 @@ def homo_warping(src_fea, src_proj, ref_proj, depth_values, rot_order="auto"):
     p = torch.matmul(src_proj.detach().cpu().float(), torch.inverse(ref_proj.detach().cpu().float()))
     rows = np.ascontiguousarray(p[:, :3, :4].reshape(b, 12).numpy(), np.float32)
     out = torch.empty(b, c, d, h, w, device=src_fea.device)
-    with _Span("tmvs_homo_warping"):
-        _lib.check(_lib_h().tmvs_homo_warping(_ptr(src_fea), rows.ctypes.data, _ptr(depth_values.contiguous()), b, c, d,
-                                              h, w, warp_flags(rot_order, h * w), _ptr(out), _stream()),
-                   "tmvs_homo_warping")
+    _launch("tmvs_homo_warping", src_fea, rows.ctypes.data, depth_values.contiguous(), b, c, d, h, w,
+            warp_flags(rot_order, h * w), out)
     return out
 
 
+@_on_tensor_device
 def softmax_wta(logits, hyp, clamp=(425.0, 935.0)):
     """prob, depth (clamped), depth_raw, conf (models/TransMVSNet.py:97-103,217-221)."""
     _dev(logits, "logits")
@@ -239,26 +240,22 @@ def softmax_wta(logits, hyp, clamp=(425.0, 935.0)):
     depth = torch.empty(b, h, w, device=logits.device)
     raw = torch.empty_like(depth)
     conf = torch.empty_like(depth)
-    with _Span("tmvs_softmax_wta"):
-        _lib.check(_lib_h().tmvs_softmax_wta(_ptr(logits), _ptr(hyp), b, d, h, w, ctypes.c_float(clamp[0]),
-                                             ctypes.c_float(clamp[1]), _ptr(prob), _ptr(depth), _ptr(raw), _ptr(conf),
-                                             _stream()), "tmvs_softmax_wta")
+    _launch("tmvs_softmax_wta", logits, hyp, b, d, h, w, clamp[0], clamp[1], prob, depth, raw, conf)
     return prob, depth, raw, conf
 
 
+@_on_tensor_device
 def costregnet(x, weights: "_lib.CostRegWeights", keepalive=None):
     """CostRegNet forward (models/module.py:447-456): [B,D,H,W] -> logits [B,D,H,W]."""
     _dev(x, "x")
     b, d, h, w = x.shape
-    nbytes = _lib_h().tmvs_costregnet_workspace(b, d, h, w, weights.base_ch)
-    ws = torch.empty(nbytes // 4 + 64, device=x.device)
     out = torch.empty_like(x)
-    with _Span("tmvs_costregnet"):
-        _lib.check(_lib_h().tmvs_costregnet(_ptr(x), b, d, h, w, ctypes.byref(weights), _ptr(ws), ws.numel() * 4,
-                                            _ptr(out), _stream()), "tmvs_costregnet")
+    _launch("tmvs_costregnet", x, b, d, h, w, ctypes.byref(weights),
+            *_workspace("tmvs_costregnet_workspace", b, d, h, w, weights.base_ch, device=x.device), out)
     return out
 
 
+@_on_tensor_device
 def costregnet_wta(x, weights: "_lib.CostRegWeights", hyp, clamp=(425.0, 935.0)):
     """CostRegNet -> softmax/WTA (models/module.py:447-456, TransMVSNet.py:97-103,214-221) in one
     call: prob, depth (clamped), depth_raw, conf, equal bit for bit to costregnet -> softmax_wta."""
@@ -267,17 +264,14 @@ def costregnet_wta(x, weights: "_lib.CostRegWeights", hyp, clamp=(425.0, 935.0))
     b, d, h, w = x.shape
     if tuple(hyp.shape) != (b, d, h, w):
         raise ValueError(f"costregnet_wta: hyp shape {tuple(hyp.shape)} != volume shape {(b, d, h, w)}")
-    nbytes = _lib_h().tmvs_costregnet_workspace(b, d, h, w, weights.base_ch)
-    ws = torch.empty(nbytes // 4 + 64, device=x.device)
     prob = torch.empty_like(x)
     depth = torch.empty(b, h, w, device=x.device)
     raw = torch.empty_like(depth)
     conf = torch.empty_like(depth)
-    with _Span("tmvs_costregnet"):
-        _lib.check(_lib_h().tmvs_costregnet_wta(_ptr(x), _ptr(hyp), b, d, h, w, ctypes.byref(weights), _ptr(ws),
-                                                ws.numel() * 4, ctypes.c_float(clamp[0]), ctypes.c_float(clamp[1]),
-                                                _ptr(prob), _ptr(depth), _ptr(raw), _ptr(conf), _stream()),
-                   "tmvs_costregnet_wta")
+    # costregnet's span: bench.py groups by it
+    _launch("tmvs_costregnet_wta", x, hyp, b, d, h, w, ctypes.byref(weights),
+            *_workspace("tmvs_costregnet_workspace", b, d, h, w, weights.base_ch, device=x.device), clamp[0], clamp[1],
+            prob, depth, raw, conf, span="tmvs_costregnet")
     return prob, depth, raw, conf
 
 
@@ -321,6 +315,7 @@ def _conv_out_dhw(d, h, w, stride):
     return (d, h, w) if stride == 1 else ((d - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
 
 
+@_on_tensor_device
 def conv3d_bn_relu(x, wpk, alpha, shift, cout, stride, out=None):
     """tmvs_conv3d_bn_relu: x NDHWC, wpk [27][cout][cin] -> relu(conv * alpha + shift), written to `out` when given."""
     _layer_args("conv3d_bn_relu", x, wpk, alpha, shift, cout)
@@ -328,12 +323,11 @@ def conv3d_bn_relu(x, wpk, alpha, shift, cout, stride, out=None):
     shape = (b, *_conv_out_dhw(d, h, w, stride), cout)
     _layer_like("conv3d_bn_relu", "out", out, shape, x.device)
     y = torch.empty(shape, device=x.device) if out is None else out
-    with _Span("tmvs_conv3d_bn_relu"):
-        _lib.check(_lib_h().tmvs_conv3d_bn_relu(_ptr(x), b, cin, d, h, w, _ptr(wpk), _ptr(alpha), _ptr(shift), cout,
-                                                stride, _ptr(y), _stream()), "tmvs_conv3d_bn_relu")
+    _launch("tmvs_conv3d_bn_relu", x, b, cin, d, h, w, wpk, alpha, shift, cout, stride, y)
     return y
 
 
+@_on_tensor_device
 def deconv3d_bn_relu_add(x, wpk, alpha, shift, cout, skip, out=None, route=None, max_workgroups=0):
     """tmvs_deconv3d_bn_relu_add: skip + relu(conv_transpose * alpha + shift) at twice x's extents, written to
     `out` (not skip itself) when given. route "generic" / "persistent" pins the kernel
@@ -349,23 +343,21 @@ def deconv3d_bn_relu_add(x, wpk, alpha, shift, cout, skip, out=None, route=None,
     y = torch.empty(shape, device=x.device) if out is None else out
     if route not in (None, "generic", "persistent"):
         raise ValueError(f"deconv3d_bn_relu_add: unknown route {route!r}")
-    name = "tmvs_deconv3d_bn_relu_add" + ("_" + route if route else "")
-    tail = (int(max_workgroups), _stream()) if route == "persistent" else (_stream(),)
-    with _Span(name):
-        _lib.check(getattr(_lib_h(), name)(_ptr(x), b, cin, d, h, w, _ptr(wpk), _ptr(alpha), _ptr(shift), cout,
-                                           _ptr(skip), _ptr(y), *tail), name)
+    bound = (int(max_workgroups),) if route == "persistent" else ()
+    _launch("tmvs_deconv3d_bn_relu_add" + ("_" + route if route else ""), x, b, cin, d, h, w, wpk, alpha, shift, cout,
+            skip, y, *bound)
     return y
 
 
+@_on_tensor_device
 def fmt_embed(feat_nchw, pe, out_tokens):
     """x + PE, 'n c h w -> n (h w) c' (FMT.py:152): feat [nv,C,H,W] -> tokens [nv,H*W,C] (written in place)."""
     nv, c, h, w = feat_nchw.shape
-    with _Span("tmvs_fmt_embed"):
-        _lib.check(_lib_h().tmvs_fmt_embed(_ptr(feat_nchw), c * h * w, _ptr(pe), pe.shape[1], pe.shape[2], nv, c, h, w,
-                                           _ptr(out_tokens), _stream()), "tmvs_fmt_embed")
+    _launch("tmvs_fmt_embed", feat_nchw, c * h * w, pe, pe.shape[1], pe.shape[2], nv, c, h, w, out_tokens)
     return out_tokens
 
 
+@_on_tensor_device
 def fmt_kv(source_tokens, enc_w, out=None, group_nv=None):
     """(KV, Ksum) of one encoder layer over source tokens [nv,S,32] -> [nv,160].
 
@@ -374,26 +366,27 @@ def fmt_kv(source_tokens, enc_w, out=None, group_nv=None):
     nv, s, _ = source_tokens.shape
     group_nv = nv if group_nv is None else int(group_nv)
     nbytes = _lib_h().tmvs_fmt_kv_grouped_workspace(nv, group_nv, s)
-    ws = torch.empty(max(1, nbytes // 4), device=source_tokens.device)
+    ws = torch.empty(max(1, nbytes // 4), device=source_tokens.device)  # exactly the bytes asked for
     kv = out if out is not None else torch.empty(nv, _lib.KV_NFLOATS, device=source_tokens.device)
-    with _Span("tmvs_fmt_kv"):
-        _lib.check(_lib_h().tmvs_fmt_kv_grouped(_ptr(source_tokens), nv, group_nv, s, _ptr(enc_w), _ptr(ws),
-                                                ws.numel() * 4, _ptr(kv), _stream()), "tmvs_fmt_kv_grouped")
+    # the ungrouped entry's span: bench.py groups by it
+    _launch("tmvs_fmt_kv_grouped", source_tokens, nv, group_nv, s, enc_w, ws, ws.numel() * 4, kv, span="tmvs_fmt_kv")
     return kv
 
 
+@_on_tensor_device
 def fmt_apply(x_tokens, kv, enc_w, shared_kv=False, tiles_per_wave=0):
     """Rest of EncoderLayer.forward in place on x [nv,L,32] (FMT.py:96-111).
 
     tiles_per_wave > 0 fixes the 16-token tiles each wave walks (tmvs_fmt_apply_tiled; the result is bitwise
     the same for every tiling); 0 sizes it from the kernel's occupancy."""
     nv, l, _ = x_tokens.shape
-    with _Span("tmvs_fmt_apply"):
-        _lib.check(_lib_h().tmvs_fmt_apply_tiled(_ptr(x_tokens), nv, l, _ptr(kv), 0 if shared_kv else _lib.KV_NFLOATS,
-                                                 _ptr(enc_w), int(tiles_per_wave), _stream()), "tmvs_fmt_apply")
+    # the untiled entry's span: bench.py groups by it
+    _launch("tmvs_fmt_apply_tiled", x_tokens, nv, l, kv, 0 if shared_kv else _lib.KV_NFLOATS, enc_w,
+            int(tiles_per_wave), span="tmvs_fmt_apply")
     return x_tokens
 
 
+@_on_tensor_device
 def fmt_pathway(coarse_nhwc, lateral_nchw, w_reduce, w_smooth, out=None):
     """smooth(up2(reduce(coarse)) + lateral) (FMT.py:221-228): coarse [nv,h,w,cc], lateral [nv,cf,2h,2w].
 
@@ -404,13 +397,12 @@ def fmt_pathway(coarse_nhwc, lateral_nchw, w_reduce, w_smooth, out=None):
         out = torch.empty(nv, 2 * h, 2 * w, cf, device=coarse_nhwc.device)
     elif tuple(out.shape) != (nv, 2 * h, 2 * w, cf) or not out.is_contiguous():
         raise ValueError(f"fmt_pathway: out must be a contiguous [{nv},{2 * h},{2 * w},{cf}] tensor")
-    with _Span("tmvs_fmt_pathway"):
-        _lib.check(_lib_h().tmvs_fmt_pathway(_ptr(coarse_nhwc), _ptr(lateral_nchw), cf * 4 * h * w, _ptr(w_reduce),
-                                             _ptr(w_smooth), nv, cc, cf, h, w, _ptr(out), _stream()), "tmvs_fmt_pathway")
+    _launch("tmvs_fmt_pathway", coarse_nhwc, lateral_nchw, cf * 4 * h * w, w_reduce, w_smooth, nv, cc, cf, h, w, out)
     return out
 
 
 # ----------------------------------------------------------------- native orchestration
+@_on_tensor_device
 def fmt_forward(stage1_nchw, pe, enc_list, tokens=None, side_stream=None):
     """Whole FMT (models/FMT.py:147-177): stage1 [nv,32,H,W] -> tokens [nv,H*W,32].
 
@@ -421,24 +413,21 @@ def fmt_forward(stage1_nchw, pe, enc_list, tokens=None, side_stream=None):
     _dev(stage1_nchw, "stage1")
     nv, c, h, w = stage1_nchw.shape
     tokens = torch.empty(nv, h * w, c, device=stage1_nchw.device) if tokens is None else tokens
-    split = side_stream is not None and nv > 1
-    lib = _lib_h()
-    nbytes = lib.tmvs_fmt_forward_split_workspace(nv, h * w) if split else lib.tmvs_fmt_forward_workspace(nv, h * w)
-    ws = torch.empty(nbytes // 4 + 64, device=stage1_nchw.device)
+    name = "tmvs_fmt_forward_split" if side_stream is not None and nv > 1 else "tmvs_fmt_forward"
+    ws, nbytes = _workspace(name + "_workspace", nv, h * w, device=stage1_nchw.device)
     ptrs = (ctypes.c_void_p * 8)(*[e.data_ptr() for e in enc_list])
-    args = (_ptr(stage1_nchw), c * h * w, _ptr(pe), pe.shape[1], pe.shape[2], nv, h, w, ptrs, _ptr(ws), ws.numel() * 4,
-            _ptr(tokens), _stream())
-    with _Span("tmvs_fmt_forward"):
-        if split:
-            _lib.check(lib.tmvs_fmt_forward_split(*args, side_stream.cuda_stream), "tmvs_fmt_forward_split")
-            if not torch.cuda.is_current_stream_capturing():  # allocator: ws / tokens are also used on the side stream
-                ws.record_stream(side_stream)
-                tokens.record_stream(side_stream)
-        else:
-            _lib.check(lib.tmvs_fmt_forward(*args), "tmvs_fmt_forward")
+    args = (stage1_nchw, c * h * w, pe, pe.shape[1], pe.shape[2], nv, h, w, ptrs, ws, nbytes, tokens)
+    if name == "tmvs_fmt_forward":
+        _launch(name, *args)
+    else:  # the side stream follows the current one; the span is the unsplit entry's: bench.py groups by it
+        _call(name, *args, _stream(), side_stream.cuda_stream, span="tmvs_fmt_forward")
+        if not torch.cuda.is_current_stream_capturing():  # allocator: ws / tokens are also used on the side stream
+            ws.record_stream(side_stream)
+            tokens.record_stream(side_stream)
     return tokens
 
 
+@_on_tensor_device
 def depth_stage(depth_values, prev_depth, feat_nhwc, ndepth, ratio, full_hw, stage_scale, proj12, pw_params,
                 view_w, vw_shift, cr_weights, clamp=(425.0, 935.0), rot_order="auto"):
     """One cascade stage for one sample (models/TransMVSNet.py:174-221). feat [N,h,w,C] NHWC.
@@ -456,18 +445,14 @@ def depth_stage(depth_values, prev_depth, feat_nhwc, ndepth, ratio, full_hw, sta
     depth = torch.empty(1, h, w, device=dev)
     raw = torch.empty_like(depth)
     conf = torch.empty_like(depth)
-    nbytes = _lib_h().tmvs_depth_stage_workspace(ndepth, h, w, cr_weights.base_ch)
-    ws = torch.empty(nbytes // 4 + 64, device=dev)
     proj = np.ascontiguousarray(proj12, np.float32).reshape(n - 1, 12)
     pw = None if pw_params is None else np.ascontiguousarray(pw_params, np.float32)
     ph, pwd = (prev_depth.shape[-2], prev_depth.shape[-1]) if prev_depth is not None else (0, 0)
-    with _Span("tmvs_depth_stage"):
-        _lib.check(_lib_h().tmvs_depth_stage(_ptr(depth_values), depth_values.shape[-1], _ptr(prev_depth), ph, pwd,
-                                             _ptr(feat_nhwc), n, c, ndepth, ctypes.c_float(ratio), full_hw[0], full_hw[1],
-                                             stage_scale, proj.ctypes.data, None if pw is None else pw.ctypes.data,
-                                             _ptr(view_w), vw_shift, warp_flags(rot_order, h * w), ctypes.byref(cr_weights), _ptr(ws), ws.numel() * 4,
-                                             ctypes.c_float(clamp[0]), ctypes.c_float(clamp[1]), _ptr(hyp), _ptr(prob),
-                                             _ptr(depth), _ptr(raw), _ptr(conf), _stream()), "tmvs_depth_stage")
+    _launch("tmvs_depth_stage", depth_values, depth_values.shape[-1], prev_depth, ph, pwd, feat_nhwc, n, c, ndepth,
+            ratio, full_hw[0], full_hw[1], stage_scale, proj.ctypes.data, None if pw is None else pw.ctypes.data,
+            view_w, vw_shift, warp_flags(rot_order, h * w), ctypes.byref(cr_weights),
+            *_workspace("tmvs_depth_stage_workspace", ndepth, h, w, cr_weights.base_ch, device=dev), clamp[0], clamp[1],
+            hyp, prob, depth, raw, conf)
     return {"depth": depth, "photo_confidence": conf, "prob_volume": prob, "depth_values": hyp}, raw
 
 
@@ -481,6 +466,7 @@ def deform_conv2d_pack(weight):
     return torch.from_numpy(out)
 
 
+@_on_tensor_device
 def deform_conv2d(x_nhwc, offset_mask, w_packed, bias, cout, bn=None, relu=False, want_nhwc=False):
     """DCN.forward's deform_conv2d (models/dcn.py:71-80) + optional folded BN / ReLU of the head.
 
@@ -495,13 +481,12 @@ def deform_conv2d(x_nhwc, offset_mask, w_packed, bias, cout, bn=None, relu=False
     out = torch.empty(b, cout, h, w, device=x_nhwc.device)
     out_nhwc = torch.empty(b, h, w, cout, device=x_nhwc.device) if want_nhwc else None
     alpha, shift = bn if bn is not None else (None, None)
-    with _Span("tmvs_deform_conv2d"):
-        _lib.check(_lib_h().tmvs_deform_conv2d(_ptr(x_nhwc), _ptr(offset_mask), _ptr(w_packed), _ptr(bias),
-                                               _ptr(alpha), _ptr(shift), int(relu), b, cin, cout, h, w, _ptr(out),
-                                               _ptr(out_nhwc), _stream()), "tmvs_deform_conv2d")
+    _launch("tmvs_deform_conv2d", x_nhwc, offset_mask, w_packed, bias, alpha, shift, int(relu), b, cin, cout, h, w, out,
+            out_nhwc)
     return (out, out_nhwc) if want_nhwc else out
 
 
+@_on_tensor_device
 def dcn_fused(x_nhwc, wom_packed, bom, w_packed, bias, cout, bn=None, relu=False, want_nchw=True, want_nhwc=False):
     """The whole DCN.forward (models/dcn.py:66-80): conv_offset_mask computed in-kernel, then the
     modulated deformable conv + optional folded BN / ReLU. x_nhwc [B,H,W,32] -> out [B,cout,H,W]
@@ -516,13 +501,12 @@ def dcn_fused(x_nhwc, wom_packed, bom, w_packed, bias, cout, bn=None, relu=False
     out = torch.empty(b, cout, h, w, device=x_nhwc.device) if want_nchw else None
     out_nhwc = torch.empty(b, h, w, cout, device=x_nhwc.device) if want_nhwc else None
     alpha, shift = bn if bn is not None else (None, None)
-    with _Span("tmvs_dcn_fused"):
-        _lib.check(_lib_h().tmvs_dcn_fused(_ptr(x_nhwc), _ptr(wom_packed), _ptr(bom), _ptr(w_packed), _ptr(bias),
-                                           _ptr(alpha), _ptr(shift), int(relu), b, cin, cout, h, w, _ptr(out),
-                                           _ptr(out_nhwc), _stream()), "tmvs_dcn_fused")
+    _launch("tmvs_dcn_fused", x_nhwc, wom_packed, bom, w_packed, bias, alpha, shift, int(relu), b, cin, cout, h, w, out,
+            out_nhwc)
     return out, out_nhwc
 
 
+@_on_tensor_device
 def conv3x3_nhwc(x_nhwc, w_packed, bn=None, relu=False, bias=None, want_nchw=False, want_nhwc=True):
     """Conv2d(32, 32, 3, 1, 1) [+ bias] + folded BN + ReLU on x_nhwc [B,H,W,32] (models/module.py:24-61).
     Returns (out_nchw, out_nhwc), None where not requested."""
@@ -534,13 +518,11 @@ def conv3x3_nhwc(x_nhwc, w_packed, bn=None, relu=False, bias=None, want_nchw=Fal
     out = torch.empty(b, 32, h, w, device=x_nhwc.device) if want_nchw else None
     out_nhwc = torch.empty(b, h, w, 32, device=x_nhwc.device) if want_nhwc else None
     alpha, shift = bn if bn is not None else (None, None)
-    with _Span("tmvs_conv3x3_nhwc"):
-        _lib.check(_lib_h().tmvs_conv3x3_nhwc(_ptr(x_nhwc), _ptr(w_packed), _ptr(bias), _ptr(alpha), _ptr(shift),
-                                              int(relu), b, cin, 32, h, w, _ptr(out), _ptr(out_nhwc), _stream()),
-                   "tmvs_conv3x3_nhwc")
+    _launch("tmvs_conv3x3_nhwc", x_nhwc, w_packed, bias, alpha, shift, int(relu), b, cin, 32, h, w, out, out_nhwc)
     return out, out_nhwc
 
 
+@_on_tensor_device
 def conv3x3_nhwc_acc(x_nhwc, w_packed, out_nhwc):
     """out_nhwc [B,H,W,32] += Conv2d(32, 32, 3, 1, 1, bias=False)(x_nhwc) in the conv's epilogue
     (tmvs_conv3x3_nhwc_acc; each element out + conv, as out.add_(conv))."""
@@ -549,12 +531,11 @@ def conv3x3_nhwc_acc(x_nhwc, w_packed, out_nhwc):
     if not x_nhwc.is_contiguous() or not out_nhwc.is_contiguous() or out_nhwc.shape != x_nhwc.shape:
         raise ValueError("conv3x3_nhwc_acc: expects contiguous x_nhwc and out_nhwc [B,H,W,32] of one shape")
     b, h, w, cin = x_nhwc.shape
-    with _Span("tmvs_conv3x3_nhwc_acc"):
-        _lib.check(_lib_h().tmvs_conv3x3_nhwc_acc(_ptr(x_nhwc), _ptr(w_packed), b, cin, 32, h, w, _ptr(out_nhwc),
-                                                  _stream()), "tmvs_conv3x3_nhwc_acc")
+    _launch("tmvs_conv3x3_nhwc_acc", x_nhwc, w_packed, b, cin, 32, h, w, out_nhwc)
     return out_nhwc
 
 
+@_on_tensor_device
 def fpn_merge(prev_nhwc, lat_nhwc, w_inner, b_inner):
     """interpolate(prev, 2, nearest) + Conv2d_1x1(lat) (models/module.py:409-417), all NHWC:
     prev [B,h,w,32], lat [B,2h,2w,cl] (cl 8/16), w_inner [32,cl] -> [B,2h,2w,32]."""
@@ -566,9 +547,7 @@ def fpn_merge(prev_nhwc, lat_nhwc, w_inner, b_inner):
             or not lat_nhwc.is_contiguous():
         raise ValueError("fpn_merge: expects contiguous prev [B,h,w,32] and lat [B,2h,2w,cl]")
     out = torch.empty(b, 2 * h, 2 * w, 32, device=prev_nhwc.device)
-    with _Span("tmvs_fpn_merge"):
-        _lib.check(_lib_h().tmvs_fpn_merge(_ptr(prev_nhwc), _ptr(lat_nhwc), cl, _ptr(w_inner), _ptr(b_inner), b, h, w,
-                                           _ptr(out), _stream()), "tmvs_fpn_merge")
+    _launch("tmvs_fpn_merge", prev_nhwc, lat_nhwc, cl, w_inner, b_inner, b, h, w, out)
     return out
 
 
@@ -581,6 +560,7 @@ def conv2d_pack(weight):
     return torch.from_numpy(out)
 
 
+@_on_tensor_device
 def conv2d_bn_relu(x, w_packed, cout, k, stride, bn=None, relu=True, nchw_input=False):
     """Conv2d(k, stride, padding k//2, no bias) + folded BN + ReLU (models/module.py:24-61) -> NHWC.
     x: NHWC [B,H,W,Ci], or the NCHW image [B,3,H,W] with nchw_input=True."""
@@ -596,12 +576,11 @@ def conv2d_bn_relu(x, w_packed, cout, k, stride, bn=None, relu=True, nchw_input=
     ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
     out = torch.empty(b, ho, wo, cout, device=x.device)
     alpha, shift = bn if bn is not None else (None, None)
-    with _Span("tmvs_conv2d_bn_relu"):
-        _lib.check(_lib_h().tmvs_conv2d_bn_relu(_ptr(x), b, cin, h, w, _ptr(w_packed), cout, k, stride, _ptr(alpha),
-                                                _ptr(shift), int(relu), _ptr(out), _stream()), "tmvs_conv2d_bn_relu")
+    _launch("tmvs_conv2d_bn_relu", x, b, cin, h, w, w_packed, cout, k, stride, alpha, shift, int(relu), out)
     return out
 
 
+@_on_tensor_device
 def entropy_loss(prob, depth_values, depth_gt, mask, grad_scale=0.0, want_grad=False, wta=None, conf=None, grad=None):
     """One stage's entropy_loss (models/module.py:495-531) + smooth-L1 depth loss (:549), and with
     want_grad the gradient of grad_scale * loss w.r.t. the stage's softmax logits.
@@ -621,8 +600,6 @@ def entropy_loss(prob, depth_values, depth_gt, mask, grad_scale=0.0, want_grad=F
         raise ValueError("depth_values must be [B,D,H,W] or [B,D]")
     if tuple(depth_gt.shape) != (b, h, w) or tuple(mask.shape) != (b, h, w):
         raise ValueError("depth_gt and mask must be [B,H,W]")
-    nbytes = _lib_h().tmvs_entropy_loss_workspace(b, h, w)
-    ws = torch.empty(nbytes // 4 + 64, device=prob.device)
     out = torch.empty(2, device=prob.device)
     if grad is not None and not want_grad:
         raise ValueError("entropy_loss: grad given without want_grad")
@@ -633,14 +610,12 @@ def entropy_loss(prob, depth_values, depth_gt, mask, grad_scale=0.0, want_grad=F
     for t, n, shape in ((wta, "wta", (b, h, w)), (conf, "conf", (b, h, w)), (grad, "grad", (b, d, h, w))):
         if t is not None and (tuple(t.shape) != shape or t.device != prob.device):
             raise ValueError(f"entropy_loss: {n} must be a contiguous {list(shape)} tensor on prob's device")
-    with _Span("tmvs_entropy_loss"):
-        _lib.check(_lib_h().tmvs_entropy_loss(_ptr(prob), _ptr(depth_values), per_pixel, _ptr(depth_gt), _ptr(mask), b,
-                                              d, h, w, ctypes.c_float(grad_scale), _ptr(ws), ws.numel() * 4,
-                                              _ptr(out), _ptr(wta), _ptr(conf), _ptr(grad), _stream()),
-                   "tmvs_entropy_loss")
+    _launch("tmvs_entropy_loss", prob, depth_values, per_pixel, depth_gt, mask, b, d, h, w, grad_scale,
+            *_workspace("tmvs_entropy_loss_workspace", b, h, w, device=prob.device), out, wta, conf, grad)
     return out[0], out[1], wta, conf, grad
 
 
+@_on_tensor_device
 def depth_metrics(depth, depth_gt, mask, depth_interval):
     """focal_loss_bld's epe / less1 / less3 (models/module.py:581-587) -> tensor [3]."""
     for t, n in ((depth, "depth"), (depth_gt, "depth_gt"), (mask, "mask")):
@@ -648,13 +623,9 @@ def depth_metrics(depth, depth_gt, mask, depth_interval):
     if depth.shape != depth_gt.shape or depth.shape != mask.shape:
         raise ValueError("depth, depth_gt and mask must have one shape")
     n = depth.numel()
-    nbytes = _lib_h().tmvs_depth_metrics_workspace(n)
-    ws = torch.empty(nbytes // 4 + 64, device=depth.device)
     out = torch.empty(3, device=depth.device)
-    with _Span("tmvs_depth_metrics"):
-        _lib.check(_lib_h().tmvs_depth_metrics(_ptr(depth), _ptr(depth_gt), _ptr(mask), n,
-                                               ctypes.c_float(float(depth_interval)), _ptr(ws), ws.numel() * 4,
-                                               _ptr(out), _stream()), "tmvs_depth_metrics")
+    _launch("tmvs_depth_metrics", depth, depth_gt, mask, n, float(depth_interval),
+            *_workspace("tmvs_depth_metrics_workspace", n, device=depth.device), out)
     return out
 
 
@@ -663,6 +634,7 @@ EVAL_METRIC_NAMES = ("abs_depth_error", "thres2mm_error", "thres4mm_error", "thr
                      "thres14mm_abserror", "thres20mm_abserror", "thres>20mm_abserror")  # train.py:216-228
 
 
+@_on_tensor_device
 def depth_eval_metrics(depth_est, depth_gt, mask, out=None):
     """The twelve DTU validation scalars of train.py:216-228 (EVAL_METRIC_NAMES) -> device tensor [12]; no
     host sync. `out`: a caller-provided contiguous float32 [12] (a row of a per-interval log buffer)."""
@@ -672,17 +644,16 @@ def depth_eval_metrics(depth_est, depth_gt, mask, out=None):
         raise ValueError("depth_est, depth_gt and mask must have one shape")
     n = depth_est.numel()
     nbytes = _lib_h().tmvs_depth_eval_metrics_workspace(n)
-    ws = torch.empty(nbytes // 8 + 8, dtype=torch.float64, device=depth_est.device)
+    ws = torch.empty(nbytes // 8 + 8, dtype=torch.float64, device=depth_est.device)  # the kernel's doubles
     if out is None:
         out = torch.empty(12, device=depth_est.device)
     elif tuple(out.shape) != (12,) or out.device != depth_est.device:
         raise ValueError("depth_eval_metrics: out must be a contiguous [12] tensor on depth_est's device")
-    with _Span("tmvs_depth_eval_metrics"):
-        _lib.check(_lib_h().tmvs_depth_eval_metrics(_ptr(depth_est), _ptr(depth_gt), _ptr(mask), n, _ptr(ws),
-                                                    ws.numel() * 8, _ptr(out), _stream()), "tmvs_depth_eval_metrics")
+    _launch("tmvs_depth_eval_metrics", depth_est, depth_gt, mask, n, ws, ws.numel() * 8, out)
     return out
 
 
+@_on_tensor_device
 def gt_pyramid(depth_raw, rows, cols, mode="bld", depth_min=0.0, depth_end=0.0, mask_png=None, target_hw=(512, 640)):
     """tmvs_gt_pyramid: the raw depth map [h, w] (and, mode "dtu", the raw depth_visual PNG [h, w] uint8) ->
     ({stage: depth}, {stage: mask}), float32 [H, W] maps at the three stage sizes. rows / cols: the int32
@@ -712,26 +683,14 @@ def gt_pyramid(depth_raw, rows, cols, mode="bld", depth_min=0.0, depth_end=0.0, 
         raise ValueError("gt_pyramid: rows / cols do not hold one entry per output row / column of the 3 stages")
     depth = {f"stage{3 - s}": torch.empty(h3 >> s, w3 >> s, device=depth_raw.device) for s in range(3)}
     mask = {k: torch.empty_like(v) for k, v in depth.items()}
-    with _Span("tmvs_gt_pyramid"):
-        _lib.check(_lib_h().tmvs_gt_pyramid(_lib.GT_DTU if mode == "dtu" else _lib.GT_BLD, _ptr(depth_raw),
-                                            _ptr(mask_png if mode == "dtu" else None), h, w, h3, w3,
-                                            ctypes.c_float(depth_min), ctypes.c_float(depth_end), _ptr(rows),
-                                            _ptr(cols), _ptr(depth["stage3"]), _ptr(depth["stage2"]),
-                                            _ptr(depth["stage1"]), _ptr(mask["stage3"]), _ptr(mask["stage2"]),
-                                            _ptr(mask["stage1"]), _stream()), "tmvs_gt_pyramid")
+    _launch("tmvs_gt_pyramid", _lib.GT_DTU if mode == "dtu" else _lib.GT_BLD, depth_raw,
+            mask_png if mode == "dtu" else None, h, w, h3, w3, depth_min, depth_end, rows, cols, depth["stage3"],
+            depth["stage2"], depth["stage1"], mask["stage3"], mask["stage2"], mask["stage1"])
     return depth, mask
 
 
-for _name in ("depth_eval_metrics", "gt_pyramid", "stage_hypotheses", "warp_corr", "aggregate_finalize", "homo_warping", "softmax_wta", "costregnet",
-              "costregnet_wta",
-              "conv3d_bn_relu", "deconv3d_bn_relu_add", "fmt_embed", "fmt_kv", "fmt_apply", "fmt_pathway",
-              "fmt_forward", "depth_stage", "deform_conv2d", "dcn_fused", "conv3x3_nhwc", "fpn_merge",
-              "conv2d_bn_relu", "entropy_loss", "depth_metrics"):
-    globals()[_name] = _on_tensor_device(globals()[_name])
-del _name
-
-
 # ----------------------------------------------------------------- CostRegNet training (train.py)
+@_on_tensor_device
 def conv3d_generic(x, w_packed, cout, out_dhw, stride, transposed=False, out=None):
     """tmvs_conv3d_generic: x NDHWC [B,D,H,W,Cin], w_packed [27][cout][Cin] -> y [B,*out_dhw,cout]
     (accumulated into `out` when given)."""
@@ -744,9 +703,8 @@ def conv3d_generic(x, w_packed, cout, out_dhw, stride, transposed=False, out=Non
     y = torch.empty(b, *out_dhw, cout, device=x.device) if out is None else out
     if tuple(y.shape) != (b, *out_dhw, cout) or not y.is_contiguous():
         raise ValueError("conv3d_generic: out must be a contiguous [B, D, H, W, cout] tensor")
-    with _Span("tmvs_conv3d_generic"):
-        _lib.check(_lib_h().tmvs_conv3d_generic(_ptr(x), b, cin, d, h, w, _ptr(w_packed), cout, out_dhw[0], out_dhw[1],
-                                                out_dhw[2], stride, flags, _ptr(y), _stream()), "tmvs_conv3d_generic")
+    _launch("tmvs_conv3d_generic", x, b, cin, d, h, w, w_packed, cout, out_dhw[0], out_dhw[1], out_dhw[2], stride,
+            flags, y)
     return y
 
 
@@ -764,6 +722,7 @@ def prob_pack(w27):
     return torch.cat([pairs, single], 1).contiguous()
 
 
+@_on_tensor_device
 def conv3d_mfma(x, w_packed, cout, stride, transposed=False, skip=None, out=None):
     """tmvs_conv3d_mfma: x NDHWC [B,D,H,W,Cin], w_packed [27][cout][Cin] -> y [B,D',H',W',cout], the raw
     convolution (no BN / ReLU) on the inference MFMA kernels; transposed = ConvTranspose3d k3 s2 p1 op1
@@ -780,12 +739,11 @@ def conv3d_mfma(x, w_packed, cout, stride, transposed=False, skip=None, out=None
     elif tuple(w_packed.shape) != (27, cout, cin):
         raise ValueError("conv3d_mfma: w_packed must be [27, cout, cin]")
     y = torch.empty(shape, device=x.device) if out is None else out
-    with _Span("tmvs_conv3d_mfma"):
-        _lib.check(_lib_h().tmvs_conv3d_mfma(_ptr(x), b, cin, d, h, w, _ptr(w_packed), cout, stride,
-                                             int(transposed), _ptr(skip), _ptr(y), _stream()), "tmvs_conv3d_mfma")
+    _launch("tmvs_conv3d_mfma", x, b, cin, d, h, w, w_packed, cout, stride, int(transposed), skip, y)
     return y
 
 
+@_on_tensor_device
 def conv3d_wgrad(direct, gathered, stride):
     """tmvs_conv3d_wgrad: direct [B,pd,ph,pw,A], gathered [B,gd,gh,gw,BC] -> dw [27][A][BC]."""
     _dev(direct, "direct")
@@ -794,16 +752,13 @@ def conv3d_wgrad(direct, gathered, stride):
     gb, gd, gh, gw, bc = gathered.shape
     if gb != b:
         raise ValueError("conv3d_wgrad: direct and gathered must have the same batch size")
-    nbytes = _lib_h().tmvs_conv3d_wgrad_workspace(b, pd, ph, pw, a, bc)
-    ws = torch.empty(nbytes // 4 + 64, device=direct.device)
     dw = torch.empty(27, a, bc, device=direct.device)
-    with _Span("tmvs_conv3d_wgrad"):
-        _lib.check(_lib_h().tmvs_conv3d_wgrad(_ptr(direct), a, b, pd, ph, pw, _ptr(gathered), bc, gd, gh, gw, stride,
-                                              _ptr(ws), ws.numel() * 4, _ptr(dw), _stream()), "tmvs_conv3d_wgrad")
+    _launch("tmvs_conv3d_wgrad", direct, a, b, pd, ph, pw, gathered, bc, gd, gh, gw, stride,
+            *_workspace("tmvs_conv3d_wgrad_workspace", b, pd, ph, pw, a, bc, device=direct.device), dw)
     return dw
 
 
-def _bn_shapes(what, z, per_channel, like_z, groups=1):
+def _bn_shapes(what, z, per_channel, like_z):
     """the statistics / affine vectors hold groups * C (or C) floats and the element-wise tensors z's count:
     the entry points take one size for all of them"""
     c = z.shape[-1]
@@ -815,107 +770,85 @@ def _bn_shapes(what, z, per_channel, like_z, groups=1):
             raise ValueError(f"{what}: {name} must have z's size")
 
 
-def _bn_ws(nvox, c, device):
-    return torch.empty(_lib_h().tmvs_bn_train_workspace(nvox, c) // 4 + 64, device=device)
-
-
-def bn_stats(z):
-    """tmvs_bn_stats: z [..., C] -> (batch mean [C], biased variance [C])."""
-    _dev(z, "z")
+def _bn_groups(z, g):
+    """(leading size arguments, entry suffix, voxels per group, C) of the plain (g None) or per-group entries"""
     c = z.shape[-1]
-    nvox = z.numel() // c
-    ws = _bn_ws(nvox, c, z.device)
-    mean = torch.empty(c, device=z.device)
-    var = torch.empty(c, device=z.device)
-    with _Span("tmvs_bn_stats"):
-        _lib.check(_lib_h().tmvs_bn_stats(_ptr(z), nvox, c, _ptr(ws), ws.numel() * 4, _ptr(mean), _ptr(var), _stream()),
-                   "tmvs_bn_stats")
+    return ((), "", z.numel() // c, c) if g is None else ((g,), "_grouped", z.numel() // (g * c), c)
+
+
+def _bn_stats_launch(z, g):
+    _dev(z, "z")
+    lead, sfx, nvox, c = _bn_groups(z, g)
+    mean = torch.empty(*lead, c, device=z.device)
+    var = torch.empty(*lead, c, device=z.device)
+    _launch("tmvs_bn_stats" + sfx, z, *lead, nvox, c,
+            *_workspace("tmvs_bn_train_workspace" + sfx, *lead, nvox, c, device=z.device), mean, var)
     return mean, var
 
 
-def bn_relu_train(z, mean, var, gamma, beta, eps, skip=None, out=None):
-    """tmvs_bn_relu_train: relu(BN_batch(z)) [+ skip], z [..., C] (written into `out` when given)."""
-    for t, n in ((z, "z"), (mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta"), (skip, "skip"), (out, "out")):
+def _bn_relu_train_launch(z, g, mean, var, gamma, beta, eps, skip=None, out=None):
+    for t, n in ((z, "z"), (mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta"), (skip, "skip"),
+                 (out, "out")):
         _dev(t, n)
-    c = z.shape[-1]
-    _bn_shapes("bn_relu_train", z, (("mean", mean, 1), ("var", var, 1), ("gamma", gamma, 1), ("beta", beta, 1)),
-               (("skip", skip), ("out", out)))
+    lead, sfx, nvox, c = _bn_groups(z, g)
+    _bn_shapes("bn_relu_train" + sfx, z, (("mean", mean, g or 1), ("var", var, g or 1), ("gamma", gamma, 1),
+                                          ("beta", beta, 1)), (("skip", skip), ("out", out)))
     out = torch.empty_like(z) if out is None else out
-    with _Span("tmvs_bn_relu_train"):
-        _lib.check(_lib_h().tmvs_bn_relu_train(_ptr(z), z.numel() // c, c, _ptr(mean), _ptr(var), _ptr(gamma),
-                                               _ptr(beta), ctypes.c_float(eps), _ptr(skip), _ptr(out), _stream()),
-                   "tmvs_bn_relu_train")
+    _launch("tmvs_bn_relu_train" + sfx, z, *lead, nvox, c, mean, var, gamma, beta, eps, skip, out)
     return out
 
 
-def bn_relu_backward(dy, z, mean, var, gamma, beta, eps, dz=None):
-    """tmvs_bn_relu_backward -> (dz, dgamma, dbeta) (dz written into `dz` when given)."""
+def _bn_relu_backward_launch(dy, z, g, mean, var, gamma, beta, eps, dz=None):
     for t, n in ((dy, "dy"), (z, "z"), (mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta"), (dz, "dz")):
         _dev(t, n)
-    c = z.shape[-1]
-    _bn_shapes("bn_relu_backward", z, (("mean", mean, 1), ("var", var, 1), ("gamma", gamma, 1), ("beta", beta, 1)),
-               (("dy", dy), ("dz", dz)))
-    nvox = z.numel() // c
-    ws = _bn_ws(nvox, c, z.device)
+    lead, sfx, nvox, c = _bn_groups(z, g)
+    _bn_shapes("bn_relu_backward" + sfx, z, (("mean", mean, g or 1), ("var", var, g or 1), ("gamma", gamma, 1),
+                                             ("beta", beta, 1)), (("dy", dy), ("dz", dz)))
     dz = torch.empty_like(z) if dz is None else dz
     dg = torch.empty(c, device=z.device)
     db = torch.empty(c, device=z.device)
-    with _Span("tmvs_bn_relu_backward"):
-        _lib.check(_lib_h().tmvs_bn_relu_backward(_ptr(dy), _ptr(z), nvox, c, _ptr(mean), _ptr(var), _ptr(gamma),
-                                                  _ptr(beta), ctypes.c_float(eps), _ptr(ws), ws.numel() * 4, _ptr(dz),
-                                                  _ptr(dg), _ptr(db), _stream()), "tmvs_bn_relu_backward")
+    _launch("tmvs_bn_relu_backward" + sfx, dy, z, *lead, nvox, c, mean, var, gamma, beta, eps,
+            *_workspace("tmvs_bn_train_workspace" + sfx, *lead, nvox, c, device=z.device), dz, dg, db)
     return dz, dg, db
 
 
+@_on_tensor_device
+def bn_stats(z):
+    """tmvs_bn_stats: z [..., C] -> (batch mean [C], biased variance [C])."""
+    return _bn_stats_launch(z, None)
+
+
+@_on_tensor_device
+def bn_relu_train(z, mean, var, gamma, beta, eps, skip=None, out=None):
+    """tmvs_bn_relu_train: relu(BN_batch(z)) [+ skip], z [..., C] (written into `out` when given)."""
+    return _bn_relu_train_launch(z, None, mean, var, gamma, beta, eps, skip, out)
+
+
+@_on_tensor_device
+def bn_relu_backward(dy, z, mean, var, gamma, beta, eps, dz=None):
+    """tmvs_bn_relu_backward -> (dz, dgamma, dbeta) (dz written into `dz` when given)."""
+    return _bn_relu_backward_launch(dy, z, None, mean, var, gamma, beta, eps, dz)
+
+
+@_on_tensor_device
 def bn_stats_grouped(z):
     """tmvs_bn_stats_grouped: z [G, ..., C] -> (mean [G, C], biased variance [G, C]), statistics per group."""
-    _dev(z, "z")
-    g, c = z.shape[0], z.shape[-1]
-    nvox = z.numel() // (g * c)
-    ws = torch.empty(_lib_h().tmvs_bn_train_workspace_grouped(g, nvox, c) // 4 + 64, device=z.device)
-    mean = torch.empty(g, c, device=z.device)
-    var = torch.empty(g, c, device=z.device)
-    with _Span("tmvs_bn_stats_grouped"):
-        _lib.check(_lib_h().tmvs_bn_stats_grouped(_ptr(z), g, nvox, c, _ptr(ws), ws.numel() * 4, _ptr(mean), _ptr(var),
-                                                  _stream()), "tmvs_bn_stats_grouped")
-    return mean, var
+    return _bn_stats_launch(z, z.shape[0])
 
 
+@_on_tensor_device
 def bn_relu_train_grouped(z, mean, var, gamma, beta, eps):
     """tmvs_bn_relu_train_grouped: relu(BN_batch(z)) per group, z [G, ..., C], mean / var [G, C]."""
-    for t, n in ((z, "z"), (mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta")):
-        _dev(t, n)
-    g, c = z.shape[0], z.shape[-1]
-    _bn_shapes("bn_relu_train_grouped", z, (("mean", mean, g), ("var", var, g), ("gamma", gamma, 1), ("beta", beta, 1)),
-               ())
-    out = torch.empty_like(z)
-    with _Span("tmvs_bn_relu_train_grouped"):
-        _lib.check(_lib_h().tmvs_bn_relu_train_grouped(_ptr(z), g, z.numel() // (g * c), c, _ptr(mean), _ptr(var),
-                                                       _ptr(gamma), _ptr(beta), ctypes.c_float(eps), None, _ptr(out),
-                                                       _stream()), "tmvs_bn_relu_train_grouped")
-    return out
+    return _bn_relu_train_launch(z, z.shape[0], mean, var, gamma, beta, eps)
 
 
+@_on_tensor_device
 def bn_relu_backward_grouped(dy, z, mean, var, gamma, beta, eps):
     """tmvs_bn_relu_backward_grouped -> (dz, dgamma, dbeta), dgamma / dbeta summed over the groups in order."""
-    for t, n in ((dy, "dy"), (z, "z"), (mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta")):
-        _dev(t, n)
-    g, c = z.shape[0], z.shape[-1]
-    _bn_shapes("bn_relu_backward_grouped", z,
-               (("mean", mean, g), ("var", var, g), ("gamma", gamma, 1), ("beta", beta, 1)), (("dy", dy),))
-    nvox = z.numel() // (g * c)
-    ws = torch.empty(_lib_h().tmvs_bn_train_workspace_grouped(g, nvox, c) // 4 + 64, device=z.device)
-    dz = torch.empty_like(z)
-    dg = torch.empty(c, device=z.device)
-    db = torch.empty(c, device=z.device)
-    with _Span("tmvs_bn_relu_backward_grouped"):
-        _lib.check(_lib_h().tmvs_bn_relu_backward_grouped(_ptr(dy), _ptr(z), g, nvox, c, _ptr(mean), _ptr(var),
-                                                          _ptr(gamma), _ptr(beta), ctypes.c_float(eps), _ptr(ws),
-                                                          ws.numel() * 4, _ptr(dz), _ptr(dg), _ptr(db), _stream()),
-                   "tmvs_bn_relu_backward_grouped")
-    return dz, dg, db
+    return _bn_relu_backward_launch(dy, z, z.shape[0], mean, var, gamma, beta, eps)
 
 
+@_on_tensor_device
 def warp_corr_backward(ref_nhwc, src_nhwc, proj12, hyp, dsim, rot_order="auto", planes=False, dref_out=None,
                        dsrc_out=None):
     """tmvs_warp_corr_backward: one sample, ref [H,W,C], src [V,H,W,C] NHWC, proj12 HOST [V,12],
@@ -931,20 +864,15 @@ def warp_corr_backward(ref_nhwc, src_nhwc, proj12, hyp, dsim, rot_order="auto", 
     if tuple(dsim.shape) != (v, d, h, w) or tuple(ref_nhwc.shape) != (h, w, c):
         raise ValueError("warp_corr_backward: shapes must be ref [H,W,C], src [V,H,W,C], hyp [D,H,W], dsim [V,D,H,W]")
     proj = np.ascontiguousarray(proj12, np.float32).reshape(v, 12)
-    nbytes = _lib_h().tmvs_warp_corr_backward_workspace(v, c, h, w, hyp.shape[0])
-    ws = torch.empty(nbytes // 4 + 64, device=hyp.device)
     dref = torch.empty_like(ref_nhwc) if dref_out is None else dref_out
     dsrc = torch.empty_like(src_nhwc) if dsrc_out is None else dsrc_out
     if tuple(dref.shape) != (h, w, c) or not dref.is_contiguous():
         raise ValueError(f"dref_out must be a contiguous [{h},{w},{c}] tensor")
     if tuple(dsrc.shape) != (v, h, w, c) or not dsrc.is_contiguous():
         raise ValueError(f"dsrc_out must be a contiguous [{v},{h},{w},{c}] tensor")
-    with _Span("tmvs_warp_corr_backward"):
-        _lib.check(_lib_h().tmvs_warp_corr_backward(_ptr(ref_nhwc), _ptr(src_nhwc), proj.ctypes.data, _ptr(hyp), _ptr(dsim),
-                                                    v, c, d, h, w,
-                                                    warp_flags(rot_order, h * w) | (_lib.WARP_BWD_PLANES if planes else 0), _ptr(ws),
-                                                    ws.numel() * 4, _ptr(dref), _ptr(dsrc), _stream()),
-                   "tmvs_warp_corr_backward")
+    ws, nbytes = _workspace("tmvs_warp_corr_backward_workspace", v, c, h, w, d, device=hyp.device)
+    _launch("tmvs_warp_corr_backward", ref_nhwc, src_nhwc, proj.ctypes.data, hyp, dsim, v, c, d, h, w,
+            warp_flags(rot_order, h * w) | (_lib.WARP_BWD_PLANES if planes else 0), ws, nbytes, dref, dsrc)
     flag = ws.view(torch.int32)[2 * v * h * w * c: 2 * v * h * w * c + 1]
     return dref, dsrc, flag
 
@@ -959,10 +887,10 @@ def _pw_shaped(op, t, name, shape, like, dtype=torch.float32):
         raise ValueError(f"{op}: {name} must be a contiguous {kind} {list(shape)} tensor on sims' device, not {got}")
 
 
-def _pw_sims(op, sims):
+def _pw_sims(op, sims, batched=False):
     _dev(sims, "sims")
-    if sims.dim() != 4:
-        raise ValueError(f"{op}: sims must be [V, D, H, W], not {list(sims.shape)}")
+    if sims.dim() != 4 + batched:
+        raise ValueError(f"{op}: sims must be [{'B, ' if batched else ''}V, D, H, W], not {list(sims.shape)}")
     return sims.shape
 
 
@@ -977,22 +905,39 @@ def _vw_map_shape(op, v, h, w, vw_shift):
     return (v, h >> s, w >> s)
 
 
-def pixelwise_train_forward(sims, pwp):
-    """tmvs_pixelwise_train_forward: sims [V,D,H,W], pwp [201] -> (stats [V,48], view_w [V,H,W], dstar int32)."""
-    op = "pixelwise_train_forward"
-    v, d, h, w = _pw_sims(op, sims)
+def _pixelwise_train_forward_launch(sims, pwp, batched):
+    """sims [V,D,H,W], or [B,V,D,H,W] through the _batched entry"""
+    op = "pixelwise_train_forward" + ("_batched" if batched else "")
+    *b, v, d, h, w = _pw_sims(op, sims, batched)
     _pw_shaped(op, pwp, "pwp", (_lib.PW_NPARAMS,), sims)
-    ws = torch.empty(_lib_h().tmvs_pixelwise_train_workspace() // 4 + 64, device=sims.device)
     stats = torch.empty(v, 48, device=sims.device)
-    vw = torch.empty(v, h, w, device=sims.device)
-    dstar = torch.empty(v, h, w, device=sims.device, dtype=torch.int32)
-    with _Span("tmvs_pixelwise_train_forward"):
-        _lib.check(_lib_h().tmvs_pixelwise_train_forward(_ptr(sims), v, d, h, w, _ptr(pwp), _ptr(ws), ws.numel() * 4,
-                                                         _ptr(stats), _ptr(vw), _ptr(dstar), _stream()),
-                   "tmvs_pixelwise_train_forward")
+    vw = torch.empty(*b, v, h, w, device=sims.device)
+    dstar = torch.empty(*b, v, h, w, device=sims.device, dtype=torch.int32)
+    _launch("tmvs_" + op, sims, *b, v, d, h, w, pwp, *_workspace("tmvs_pixelwise_train_workspace", device=sims.device),
+            stats, vw, dstar)
     return stats, vw, dstar
 
 
+def _pixelwise_train_backward_launch(sims, pwp, stats, view_w, dstar, dview_w, dsims, batched):
+    op = "pixelwise_train_backward" + ("_batched" if batched else "")
+    *b, v, d, h, w = _pw_sims(op, sims, batched)
+    for t, n, shape in ((pwp, "pwp", (_lib.PW_NPARAMS,)), (stats, "stats", (v, 48)), (view_w, "view_w", (*b, v, h, w)),
+                        (dview_w, "dview_w", (*b, v, h, w)), (dsims, "dsims", (*b, v, d, h, w))):
+        _pw_shaped(op, t, n, shape, sims)
+    _pw_shaped(op, dstar, "dstar", (*b, v, h, w), sims, torch.int32)
+    dpwp = torch.zeros(_lib.PW_NPARAMS, device=sims.device)
+    _launch("tmvs_" + op, sims, *b, v, d, h, w, pwp, stats, view_w, dstar, dview_w,
+            *_workspace("tmvs_pixelwise_train_workspace", device=sims.device), dsims, dpwp)
+    return dpwp
+
+
+@_on_tensor_device
+def pixelwise_train_forward(sims, pwp):
+    """tmvs_pixelwise_train_forward: sims [V,D,H,W], pwp [201] -> (stats [V,48], view_w [V,H,W], dstar int32)."""
+    return _pixelwise_train_forward_launch(sims, pwp, False)
+
+
+@_on_tensor_device
 def aggregate_train(sims, view_w, vw_shift, sim=None):
     """tmvs_aggregate_train: sims [V,D,H,W], view_w [V,H>>s,W>>s] -> (sim [D,H,W], wsum [H,W]).
     sim: a caller-provided contiguous [D,H,W] output."""
@@ -1003,12 +948,11 @@ def aggregate_train(sims, view_w, vw_shift, sim=None):
         sim = torch.empty(d, h, w, device=sims.device)
     _pw_shaped(op, sim, "sim", (d, h, w), sims)
     wsum = torch.empty(h, w, device=sims.device)
-    with _Span("tmvs_aggregate_train"):
-        _lib.check(_lib_h().tmvs_aggregate_train(_ptr(sims), _ptr(view_w), v, d, h, w, vw_shift, _ptr(sim), _ptr(wsum),
-                                                 _stream()), "tmvs_aggregate_train")
+    _launch("tmvs_aggregate_train", sims, view_w, v, d, h, w, vw_shift, sim, wsum)
     return sim, wsum
 
 
+@_on_tensor_device
 def aggregate_train_backward(dsim, sims, sim, wsum, view_w, vw_shift, want_dview_w, dsims=None, dview_w=None):
     """tmvs_aggregate_train_backward -> (dsims [V,D,H,W], dview_w [V,H,W] or None).
     dsims / dview_w: caller-provided contiguous outputs of those shapes (dview_w only with want_dview_w)."""
@@ -1026,74 +970,31 @@ def aggregate_train_backward(dsim, sims, sim, wsum, view_w, vw_shift, want_dview
     _pw_shaped(op, dsims, "dsims", (v, d, h, w), sims)
     if want_dview_w:
         _pw_shaped(op, dview_w, "dview_w", (v, h, w), sims)
-    with _Span("tmvs_aggregate_train_backward"):
-        _lib.check(_lib_h().tmvs_aggregate_train_backward(_ptr(dsim), _ptr(sims), _ptr(sim), _ptr(wsum), _ptr(view_w), v,
-                                                          d, h, w, vw_shift, _ptr(dsims), _ptr(dview_w), _stream()),
-                   "tmvs_aggregate_train_backward")
+    _launch("tmvs_aggregate_train_backward", dsim, sims, sim, wsum, view_w, v, d, h, w, vw_shift, dsims, dview_w)
     return dsims, dview_w
 
 
+@_on_tensor_device
 def pixelwise_train_backward(sims, pwp, stats, view_w, dstar, dview_w, dsims):
     """tmvs_pixelwise_train_backward: adds the PixelwiseNet path into dsims (in place) -> dpwp [201]."""
-    op = "pixelwise_train_backward"
-    v, d, h, w = _pw_sims(op, sims)
-    for t, n, shape in ((pwp, "pwp", (_lib.PW_NPARAMS,)), (stats, "stats", (v, 48)), (view_w, "view_w", (v, h, w)),
-                        (dview_w, "dview_w", (v, h, w)), (dsims, "dsims", (v, d, h, w))):
-        _pw_shaped(op, t, n, shape, sims)
-    _pw_shaped(op, dstar, "dstar", (v, h, w), sims, torch.int32)
-    ws = torch.empty(_lib_h().tmvs_pixelwise_train_workspace() // 4 + 64, device=sims.device)
-    dpwp = torch.zeros(_lib.PW_NPARAMS, device=sims.device)
-    with _Span("tmvs_pixelwise_train_backward"):
-        _lib.check(_lib_h().tmvs_pixelwise_train_backward(_ptr(sims), v, d, h, w, _ptr(pwp), _ptr(stats), _ptr(view_w),
-                                                          _ptr(dstar), _ptr(dview_w), _ptr(ws), ws.numel() * 4,
-                                                          _ptr(dsims), _ptr(dpwp), _stream()),
-                   "tmvs_pixelwise_train_backward")
-    return dpwp
+    return _pixelwise_train_backward_launch(sims, pwp, stats, view_w, dstar, dview_w, dsims, False)
 
 
-def _pw_sims_batched(op, sims):
-    _dev(sims, "sims")
-    if sims.dim() != 5:
-        raise ValueError(f"{op}: sims must be [B, V, D, H, W], not {list(sims.shape)}")
-    return sims.shape
-
-
+@_on_tensor_device
 def pixelwise_train_forward_batched(sims, pwp):
     """tmvs_pixelwise_train_forward_batched: sims [B,V,D,H,W], pwp [201] -> (stats [V,48] joint over each view's
     B*D*H*W elements, view_w [B,V,H,W], dstar int32 [B,V,H,W])."""
-    op = "pixelwise_train_forward_batched"
-    b, v, d, h, w = _pw_sims_batched(op, sims)
-    _pw_shaped(op, pwp, "pwp", (_lib.PW_NPARAMS,), sims)
-    ws = torch.empty(_lib_h().tmvs_pixelwise_train_workspace() // 4 + 64, device=sims.device)
-    stats = torch.empty(v, 48, device=sims.device)
-    vw = torch.empty(b, v, h, w, device=sims.device)
-    dstar = torch.empty(b, v, h, w, device=sims.device, dtype=torch.int32)
-    with _Span("tmvs_pixelwise_train_forward_batched"):
-        _lib.check(_lib_h().tmvs_pixelwise_train_forward_batched(_ptr(sims), b, v, d, h, w, _ptr(pwp), _ptr(ws),
-                                                                 ws.numel() * 4, _ptr(stats), _ptr(vw), _ptr(dstar),
-                                                                 _stream()), "tmvs_pixelwise_train_forward_batched")
-    return stats, vw, dstar
+    return _pixelwise_train_forward_launch(sims, pwp, True)
 
 
+@_on_tensor_device
 def pixelwise_train_backward_batched(sims, pwp, stats, view_w, dstar, dview_w, dsims):
     """tmvs_pixelwise_train_backward_batched: sims / dsims [B,V,D,H,W], stats [V,48], view_w / dstar / dview_w
     [B,V,H,W]; adds the PixelwiseNet path into dsims (in place) -> dpwp [201]."""
-    op = "pixelwise_train_backward_batched"
-    b, v, d, h, w = _pw_sims_batched(op, sims)
-    for t, n, shape in ((pwp, "pwp", (_lib.PW_NPARAMS,)), (stats, "stats", (v, 48)), (view_w, "view_w", (b, v, h, w)),
-                        (dview_w, "dview_w", (b, v, h, w)), (dsims, "dsims", (b, v, d, h, w))):
-        _pw_shaped(op, t, n, shape, sims)
-    _pw_shaped(op, dstar, "dstar", (b, v, h, w), sims, torch.int32)
-    ws = torch.empty(_lib_h().tmvs_pixelwise_train_workspace() // 4 + 64, device=sims.device)
-    dpwp = torch.zeros(_lib.PW_NPARAMS, device=sims.device)
-    with _Span("tmvs_pixelwise_train_backward_batched"):
-        _lib.check(_lib_h().tmvs_pixelwise_train_backward_batched(_ptr(sims), b, v, d, h, w, _ptr(pwp), _ptr(stats),
-                                                                  _ptr(view_w), _ptr(dstar), _ptr(dview_w), _ptr(ws),
-                                                                  ws.numel() * 4, _ptr(dsims), _ptr(dpwp), _stream()),
-                   "tmvs_pixelwise_train_backward_batched")
-    return dpwp
+    return _pixelwise_train_backward_launch(sims, pwp, stats, view_w, dstar, dview_w, dsims, True)
 
 
+@_on_tensor_device
 def upsample2_add_nhwc(r, lateral_nchw):
     """tmvs_upsample2_add_nhwc: r [N,h,w,C] -> bilinear x2 + lateral [N,C,2h,2w] -> [N,2h,2w,C]."""
     _dev(r, "r")
@@ -1102,12 +1003,11 @@ def upsample2_add_nhwc(r, lateral_nchw):
     if tuple(lateral_nchw.shape) != (n, c, 2 * h, 2 * w):
         raise ValueError("upsample2_add_nhwc: lateral must be [N, C, 2h, 2w]")
     u = torch.empty(n, 2 * h, 2 * w, c, device=r.device)
-    with _Span("tmvs_upsample2_add_nhwc"):
-        _lib.check(_lib_h().tmvs_upsample2_add_nhwc(_ptr(r), _ptr(lateral_nchw), n, h, w, c, _ptr(u), _stream()),
-                   "tmvs_upsample2_add_nhwc")
+    _launch("tmvs_upsample2_add_nhwc", r, lateral_nchw, n, h, w, c, u)
     return u
 
 
+@_on_tensor_device
 def upsample2_backward_nhwc(du):
     """tmvs_upsample2_backward_nhwc: du [N,2h,2w,C] -> dr [N,h,w,C]."""
     _dev(du, "du")
@@ -1115,9 +1015,7 @@ def upsample2_backward_nhwc(du):
     if hh % 2 or ww % 2:
         raise ValueError("upsample2_backward_nhwc: du must be [N, 2h, 2w, C]")
     dr = torch.empty(n, hh // 2, ww // 2, c, device=du.device)
-    with _Span("tmvs_upsample2_backward_nhwc"):
-        _lib.check(_lib_h().tmvs_upsample2_backward_nhwc(_ptr(du), n, hh // 2, ww // 2, c, _ptr(dr), _stream()),
-                   "tmvs_upsample2_backward_nhwc")
+    _launch("tmvs_upsample2_backward_nhwc", du, n, hh // 2, ww // 2, c, dr)
     return dr
 
 
@@ -1128,6 +1026,7 @@ def _tokens(x, name, c=None):
     return x.shape[0]
 
 
+@_on_tensor_device
 def token_linear(x, w, b=None, transpose_w=False, relu_of=None, out=None, residual=None):
     """tmvs_token_linear: x [T,in] -> x w^T + b (w [out,in]) or, transpose_w, x w (w [in',out'] -> out = in').
 
@@ -1144,11 +1043,7 @@ def token_linear(x, w, b=None, transpose_w=False, relu_of=None, out=None, residu
                 (relu_of is not None and tuple(relu_of.shape) != (t, o_f)):
             raise ValueError("token_linear: shape mismatch")
         y = torch.empty(t, o_f, device=x.device)
-        with _Span("tmvs_token_linear_res"):
-            _lib.check(_lib_h().tmvs_token_linear_res(_ptr(x), t, x.shape[1], o_f, _ptr(w),
-                                                      _ptr(b) if b is not None else None, int(transpose_w),
-                                                      _ptr(relu_of) if relu_of is not None else None, _ptr(residual),
-                                                      _ptr(y), _stream()), "tmvs_token_linear_res")
+        _launch("tmvs_token_linear_res", x, t, x.shape[1], o_f, w, b, int(transpose_w), relu_of, residual, y)
         return y
     o_f = w.shape[0] if not transpose_w else w.shape[1]
     if x.shape[1] != (w.shape[1] if not transpose_w else w.shape[0]):
@@ -1158,13 +1053,11 @@ def token_linear(x, w, b=None, transpose_w=False, relu_of=None, out=None, residu
         if a is not None and tuple(a.shape) != (t, o_f):
             raise ValueError(f"token_linear: {n} must be [{t}, {o_f}]")
     y = out if acc else torch.empty(t, o_f, device=x.device)
-    with _Span("tmvs_token_linear"):
-        _lib.check(_lib_h().tmvs_token_linear(_ptr(x), t, x.shape[1], o_f, _ptr(w), _ptr(b) if b is not None else None,
-                                              int(transpose_w), _ptr(relu_of) if relu_of is not None else None, int(acc),
-                                              _ptr(y), _stream()), "tmvs_token_linear")
+    _launch("tmvs_token_linear", x, t, x.shape[1], o_f, w, b, int(transpose_w), relu_of, int(acc), y)
     return y
 
 
+@_on_tensor_device
 def token_wgrad(dy, x, dw=None, db=None):
     """tmvs_token_wgrad: dy [T,a], x [T,b] -> (dw [a,b] = dy^T x, db [a] = column sums of dy); accumulates into
     dw/db when both are given."""
@@ -1181,24 +1074,23 @@ def token_wgrad(dy, x, dw=None, db=None):
         _dev(z, n)
         if tuple(z.shape) != shp:
             raise ValueError(f"token_wgrad: {n} must be {shp}")
-    ws = torch.empty(_lib_h().tmvs_token_wgrad_workspace(t, a, b) // 4 + 64, device=dy.device)
-    with _Span("tmvs_token_wgrad"):
-        _lib.check(_lib_h().tmvs_token_wgrad(_ptr(dy), a, _ptr(x), b, t, _ptr(ws), ws.numel() * 4, _ptr(dw), _ptr(db),
-                                             int(acc), _stream()), "tmvs_token_wgrad")
+    _launch("tmvs_token_wgrad", dy, a, x, b, t, *_workspace("tmvs_token_wgrad_workspace", t, a, b, device=dy.device),
+            dw, db, int(acc))
     return dw, db
 
 
+@_on_tensor_device
 def layer_norm_fwd(x, g, b):
     """tmvs_layer_norm_fwd: LayerNorm(32) of x [T,32]."""
     t = _tokens(x, "x", 32)
     _dev(g, "g")
     _dev(b, "b")
     y = torch.empty_like(x)
-    with _Span("tmvs_layer_norm_fwd"):
-        _lib.check(_lib_h().tmvs_layer_norm_fwd(_ptr(x), t, _ptr(g), _ptr(b), _ptr(y), _stream()), "tmvs_layer_norm_fwd")
+    _launch("tmvs_layer_norm_fwd", x, t, g, b, y)
     return y
 
 
+@_on_tensor_device
 def layer_norm_bwd(dy, x, g, dgb=None):
     """tmvs_layer_norm_bwd: -> (dx [T,32], dgb [64] = dgamma | dbeta); accumulates into dgb when given."""
     t = _tokens(dy, "dy", 32)
@@ -1209,25 +1101,23 @@ def layer_norm_bwd(dy, x, g, dgb=None):
     acc = dgb is not None
     dgb = dgb if acc else torch.empty(64, device=dy.device)
     dx = torch.empty_like(dy)
-    ws = torch.empty(_lib_h().tmvs_layer_norm_bwd_workspace(t) // 4 + 64, device=dy.device)
-    with _Span("tmvs_layer_norm_bwd"):
-        _lib.check(_lib_h().tmvs_layer_norm_bwd(_ptr(dy), _ptr(x), t, _ptr(g), _ptr(ws), ws.numel() * 4, _ptr(dx),
-                                                _ptr(dgb), int(acc), _stream()), "tmvs_layer_norm_bwd")
+    _launch("tmvs_layer_norm_bwd", dy, x, t, g, *_workspace("tmvs_layer_norm_bwd_workspace", t, device=dy.device), dx,
+            dgb, int(acc))
     return dx, dgb
 
 
+@_on_tensor_device
 def linattn_fwd(q, kv, tokens_per_group):
     """tmvs_linattn_fwd: q [T,32] (pre-elu), kv [G,160] (G == 1: shared) -> msg [T,32]."""
     t = _tokens(q, "q", 32)
     _dev(kv, "kv")
     msg = torch.empty_like(q)
     stride = 0 if kv.shape[0] == 1 else _lib.KV_NFLOATS
-    with _Span("tmvs_linattn_fwd"):
-        _lib.check(_lib_h().tmvs_linattn_fwd(_ptr(q), t, tokens_per_group, _ptr(kv), stride, _ptr(msg), _stream()),
-                   "tmvs_linattn_fwd")
+    _launch("tmvs_linattn_fwd", q, t, tokens_per_group, kv, stride, msg)
     return msg
 
 
+@_on_tensor_device
 def linattn_bwd_q(q, dmsg, kv, tokens_per_group):
     """tmvs_linattn_bwd_q: -> (dq [T,32], dkv [T / tokens_per_group, 160])."""
     t = _tokens(q, "q", 32)
@@ -1242,13 +1132,12 @@ def linattn_bwd_q(q, dmsg, kv, tokens_per_group):
         raise ValueError("linattn_bwd_q: kv must have one row per group (or one shared row)")
     dq = torch.empty_like(q)
     dkv = torch.empty(groups, _lib.KV_NFLOATS, device=q.device)
-    ws = torch.empty(_lib_h().tmvs_linattn_bwd_workspace(t, tokens_per_group) // 4 + 64, device=q.device)
-    with _Span("tmvs_linattn_bwd_q"):
-        _lib.check(_lib_h().tmvs_linattn_bwd_q(_ptr(q), _ptr(dmsg), t, tokens_per_group, _ptr(kv), stride, _ptr(ws),
-                                               ws.numel() * 4, _ptr(dq), _ptr(dkv), _stream()), "tmvs_linattn_bwd_q")
+    _launch("tmvs_linattn_bwd_q", q, dmsg, t, tokens_per_group, kv, stride,
+            *_workspace("tmvs_linattn_bwd_workspace", t, tokens_per_group, device=q.device), dq, dkv)
     return dq, dkv
 
 
+@_on_tensor_device
 def linattn_bwd_kv(k, v, dkv, tokens_per_group):
     """tmvs_linattn_bwd_kv: k (pre-elu), v [S,32], dkv [S / tokens_per_group, 160] -> (dk, dv)."""
     s = _tokens(k, "k", 32)
@@ -1256,24 +1145,22 @@ def linattn_bwd_kv(k, v, dkv, tokens_per_group):
         raise ValueError("linattn_bwd_kv: shape mismatch")
     _dev(dkv, "dkv")
     dk, dv = torch.empty_like(k), torch.empty_like(v)
-    with _Span("tmvs_linattn_bwd_kv"):
-        _lib.check(_lib_h().tmvs_linattn_bwd_kv(_ptr(k), _ptr(v), s, tokens_per_group, _ptr(dkv), _ptr(dk), _ptr(dv),
-                                                _stream()), "tmvs_linattn_bwd_kv")
+    _launch("tmvs_linattn_bwd_kv", k, v, s, tokens_per_group, dkv, dk, dv)
     return dk, dv
 
 
+@_on_tensor_device
 def adam_step(param_flat, grad_flat, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step):
     """tmvs_adam_step: one Adam update (torch's order) of a flat fp32 parameter buffer, in place."""
     for t, n in ((param_flat, "param"), (grad_flat, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _dev(t, n)
         if t.numel() != param_flat.numel():
             raise ValueError(f"adam_step: {n} must have {param_flat.numel()} elements")
-    with _Span("tmvs_adam_step"):
-        _lib.check(_lib_h().tmvs_adam_step(_ptr(param_flat), _ptr(grad_flat), _ptr(exp_avg), _ptr(exp_avg_sq),
-                                           param_flat.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                           float(weight_decay), int(step), _stream()), "tmvs_adam_step")
+    _launch("tmvs_adam_step", param_flat, grad_flat, exp_avg, exp_avg_sq, param_flat.numel(), float(lr),
+            float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step))
 
 
+@_on_tensor_device
 def adam_step_dev(param_flat, grad_flat, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step_counter, scalars,
                   lr_dev=None):
     """tmvs_adam_step_dev: adam_step with the step number advanced on the device (graph-replayable).
@@ -1286,26 +1173,14 @@ def adam_step_dev(param_flat, grad_flat, exp_avg, exp_avg_sq, lr, betas, eps, we
         raise RuntimeError("step_counter must be a device int32 tensor")
     if lr_dev is not None and (lr_dev.dtype != torch.float64 or not lr_dev.is_cuda or lr_dev.numel() != 1):
         raise RuntimeError("lr_dev must be a device float64 tensor of one element")
-    with _Span("tmvs_adam_step"):
-        _lib.check(_lib_h().tmvs_adam_step_dev(_ptr(param_flat), _ptr(grad_flat), _ptr(exp_avg), _ptr(exp_avg_sq),
-                                               param_flat.numel(), float(lr),
-                                               _ptr(lr_dev), float(betas[0]),
-                                               float(betas[1]), float(eps), float(weight_decay), _ptr(step_counter),
-                                               _ptr(scalars),
-                                               _stream()), "tmvs_adam_step_dev")
-
-
-for _name in ("conv3d_generic", "conv3d_mfma", "conv3d_wgrad", "bn_stats", "bn_relu_train", "bn_relu_backward", "bn_stats_grouped", "bn_relu_train_grouped",
-              "bn_relu_backward_grouped", "warp_corr_backward",
-              "upsample2_add_nhwc", "upsample2_backward_nhwc", "pixelwise_train_forward", "aggregate_train", "aggregate_train_backward", "pixelwise_train_backward",
-              "pixelwise_train_forward_batched", "pixelwise_train_backward_batched",
-              "token_linear", "token_wgrad", "layer_norm_fwd", "layer_norm_bwd", "linattn_fwd", "linattn_bwd_q",
-              "linattn_bwd_kv", "adam_step", "adam_step_dev"):
-    globals()[_name] = _on_tensor_device(globals()[_name])
-del _name
+    # adam_step's span: bench.py groups by it
+    _launch("tmvs_adam_step_dev", param_flat, grad_flat, exp_avg, exp_avg_sq, param_flat.numel(), float(lr), lr_dev,
+            float(betas[0]), float(betas[1]), float(eps), float(weight_decay), step_counter, scalars,
+            span="tmvs_adam_step")
 
 
 # ----------------------------------------------------------------- FeatureNet training (featurenet_train.py)
+@_on_tensor_device
 def conv2d_generic(x, w_taps, cout, out_hw, k, stride, pad, bias=None, transposed=False, out=None):
     """tmvs_conv2d_generic: x NHWC [B,H,W,Cin], w_taps [k*k][cout][Cin] -> y [B,*out_hw,cout] (+ bias);
     accumulated into `out` when given."""
@@ -1319,13 +1194,11 @@ def conv2d_generic(x, w_taps, cout, out_hw, k, stride, pad, bias=None, transpose
     y = torch.empty(b, *out_hw, cout, device=x.device) if out is None else out
     if tuple(y.shape) != (b, *out_hw, cout) or not y.is_contiguous():
         raise ValueError("conv2d_generic: out must be a contiguous [B, H, W, cout] tensor")
-    with _Span("tmvs_conv2d_generic"):
-        _lib.check(_lib_h().tmvs_conv2d_generic(_ptr(x), b, cin, h, w, _ptr(w_taps), _ptr(bias), cout, out_hw[0],
-                                                out_hw[1], k, stride, pad, flags, _ptr(y), _stream()),
-                   "tmvs_conv2d_generic")
+    _launch("tmvs_conv2d_generic", x, b, cin, h, w, w_taps, bias, cout, out_hw[0], out_hw[1], k, stride, pad, flags, y)
     return y
 
 
+@_on_tensor_device
 def conv2d_wgrad(direct, gathered, k, stride, pad):
     """tmvs_conv2d_wgrad: direct [B,ph,pw,A] (dz), gathered [B,gh,gw,BC] (x) -> dw [k*k][A][BC]."""
     _dev(direct, "direct")
@@ -1334,27 +1207,24 @@ def conv2d_wgrad(direct, gathered, k, stride, pad):
     gb, gh, gw, bc = gathered.shape
     if gb != b:
         raise ValueError("conv2d_wgrad: direct and gathered must have the same batch size")
-    nbytes = _lib_h().tmvs_conv2d_wgrad_workspace(b, ph, pw, a, bc, k)
-    ws = torch.empty(nbytes // 4 + 64, device=direct.device)
     dw = torch.empty(k * k, a, bc, device=direct.device)
-    with _Span("tmvs_conv2d_wgrad"):
-        _lib.check(_lib_h().tmvs_conv2d_wgrad(_ptr(direct), a, b, ph, pw, _ptr(gathered), bc, gh, gw, k, stride, pad,
-                                              _ptr(ws), ws.numel() * 4, _ptr(dw), _stream()), "tmvs_conv2d_wgrad")
+    _launch("tmvs_conv2d_wgrad", direct, a, b, ph, pw, gathered, bc, gh, gw, k, stride, pad,
+            *_workspace("tmvs_conv2d_wgrad_workspace", b, ph, pw, a, bc, k, device=direct.device), dw)
     return dw
 
 
+@_on_tensor_device
 def colsum(x):
     """tmvs_colsum: x [..., C] -> [C] (sum over every other axis; C <= 32)."""
     _dev(x, "x")
     c = x.shape[-1]
     n = x.numel() // c
-    ws = torch.empty(_lib_h().tmvs_colsum_workspace(n, c) // 4 + 64, device=x.device)
     out = torch.empty(c, device=x.device)
-    with _Span("tmvs_colsum"):
-        _lib.check(_lib_h().tmvs_colsum(_ptr(x), n, c, _ptr(ws), ws.numel() * 4, _ptr(out), _stream()), "tmvs_colsum")
+    _launch("tmvs_colsum", x, n, c, *_workspace("tmvs_colsum_workspace", n, c, device=x.device), out)
     return out
 
 
+@_on_tensor_device
 def dcn_forward_train(x_nhwc, wom_packed, bom, w_packed, bias, cout, want_nchw=False):
     """tmvs_dcn_forward_train: DCN.forward without BN/ReLU -> (out_nhwc [B,H,W,cout], offset_mask
     [B,27,H,W], out_nchw or None)."""
@@ -1364,13 +1234,11 @@ def dcn_forward_train(x_nhwc, wom_packed, bom, w_packed, bias, cout, want_nchw=F
     out_nhwc = torch.empty(b, h, w, cout, device=x_nhwc.device)
     out = torch.empty(b, cout, h, w, device=x_nhwc.device) if want_nchw else None
     om = torch.empty(b, 27, h, w, device=x_nhwc.device)
-    with _Span("tmvs_dcn_forward_train"):
-        _lib.check(_lib_h().tmvs_dcn_forward_train(_ptr(x_nhwc), _ptr(wom_packed), _ptr(bom), _ptr(w_packed), _ptr(bias),
-                                                   b, cin, cout, h, w, _ptr(out), _ptr(out_nhwc), _ptr(om), _stream()),
-                   "tmvs_dcn_forward_train")
+    _launch("tmvs_dcn_forward_train", x_nhwc, wom_packed, bom, w_packed, bias, b, cin, cout, h, w, out, out_nhwc, om)
     return out_nhwc, om, out
 
 
+@_on_tensor_device
 def dcn_backward(x_nhwc, offset_mask, w_taps, dy_nhwc, dx_nhwc):
     """tmvs_dcn_backward: -> (dom [B,H,W,32] (channels 27..31 zero), dw_taps [9][cout][32]); dx_nhwc is
     accumulated into."""
@@ -1382,19 +1250,17 @@ def dcn_backward(x_nhwc, offset_mask, w_taps, dy_nhwc, dx_nhwc):
     if tuple(offset_mask.shape) != (b, 27, h, w) or tuple(dy_nhwc.shape) != (b, h, w, cout) or \
             tuple(w_taps.shape) != (9, cout, cin) or tuple(dx_nhwc.shape) != tuple(x_nhwc.shape):
         raise ValueError("dcn_backward: shape mismatch")
-    ws = torch.empty(_lib_h().tmvs_dcn_backward_workspace(b, cout, h, w) // 4 + 64, device=x_nhwc.device)
     dom = torch.empty(b, h, w, 32, device=x_nhwc.device)
     dw = torch.empty(9, cout, cin, device=x_nhwc.device)
-    with _Span("tmvs_dcn_backward"):
-        _lib.check(_lib_h().tmvs_dcn_backward(_ptr(x_nhwc), _ptr(offset_mask), _ptr(w_taps), _ptr(dy_nhwc), b, cin, cout,
-                                              h, w, _ptr(ws), ws.numel() * 4, _ptr(dx_nhwc), _ptr(dom), _ptr(dw),
-                                              _stream()), "tmvs_dcn_backward")
+    _launch("tmvs_dcn_backward", x_nhwc, offset_mask, w_taps, dy_nhwc, b, cin, cout, h, w,
+            *_workspace("tmvs_dcn_backward_workspace", b, cout, h, w, device=x_nhwc.device), dx_nhwc, dom, dw)
     return dom, dw
 
 
 _DCN_FAR = {}
 
 
+@_on_tensor_device
 def dcn_backward_set(x_nhwc, offset_mask, w_taps, dy_nhwc):
     """tmvs_dcn_backward_set: -> (dx [B,H,W,32] written, not accumulated; dom; dw_taps). The corners beyond the
     LDS windows go through a zeroed far buffer kept per (device, shape) and cleared again by the call, so no
@@ -1421,14 +1287,11 @@ def dcn_backward_set(x_nhwc, offset_mask, w_taps, dy_nhwc):
     cur = torch.cuda.current_stream(x_nhwc.device)
     if not capturing and ent[1] is not None and ent[1] != cur:  # a call on another stream: order after its use
         cur.wait_event(ent[2])
-    ws = torch.empty(_lib_h().tmvs_dcn_backward_workspace(b, cout, h, w) // 4 + 64, device=x_nhwc.device)
     dx = torch.empty_like(x_nhwc)
     dom = torch.empty(b, h, w, 32, device=x_nhwc.device)
     dw = torch.empty(9, cout, cin, device=x_nhwc.device)
-    with _Span("tmvs_dcn_backward_set"):
-        _lib.check(_lib_h().tmvs_dcn_backward_set(_ptr(x_nhwc), _ptr(offset_mask), _ptr(w_taps), _ptr(dy_nhwc), b, cin,
-                                                  cout, h, w, _ptr(ws), ws.numel() * 4, _ptr(dx), _ptr(dom), _ptr(dw),
-                                                  _ptr(far), _stream()), "tmvs_dcn_backward_set")
+    _launch("tmvs_dcn_backward_set", x_nhwc, offset_mask, w_taps, dy_nhwc, b, cin, cout, h, w,
+            *_workspace("tmvs_dcn_backward_workspace", b, cout, h, w, device=x_nhwc.device), dx, dom, dw, far)
     if not capturing:
         ev = ent[2] or torch.cuda.Event()
         ev.record(cur)
@@ -1436,6 +1299,7 @@ def dcn_backward_set(x_nhwc, offset_mask, w_taps, dy_nhwc):
     return dx, dom, dw
 
 
+@_on_tensor_device
 def nearest_up2_backward_nhwc(d, out=None):
     """tmvs_nearest_up2_backward_nhwc: d [n,2h,2w,C] -> [n,h,w,C] (accumulated into `out` when given)."""
     _dev(d, "d")
@@ -1443,29 +1307,19 @@ def nearest_up2_backward_nhwc(d, out=None):
     if h2 % 2 or w2 % 2:
         raise ValueError("nearest_up2_backward_nhwc: d must be [n, 2h, 2w, C]")
     y = torch.empty(n, h2 // 2, w2 // 2, c, device=d.device) if out is None else out
-    with _Span("tmvs_nearest_up2_backward_nhwc"):
-        _lib.check(_lib_h().tmvs_nearest_up2_backward_nhwc(_ptr(d), n, h2 // 2, w2 // 2, c, int(out is not None), _ptr(y),
-                                                           _stream()), "tmvs_nearest_up2_backward_nhwc")
+    _launch("tmvs_nearest_up2_backward_nhwc", d, n, h2 // 2, w2 // 2, c, int(out is not None), y)
     return y
 
 
+@_on_tensor_device
 def softmax_backward(prob, dprob):
     """tmvs_softmax_backward: prob, dprob [B,D,H,W] -> d logits."""
     _dev(prob, "prob")
     _dev(dprob, "dprob")
     b, d, h, w = prob.shape
     out = torch.empty_like(prob)
-    with _Span("tmvs_softmax_backward"):
-        _lib.check(_lib_h().tmvs_softmax_backward(_ptr(prob), _ptr(dprob), b, d, h, w, _ptr(out), _stream()),
-                   "tmvs_softmax_backward")
+    _launch("tmvs_softmax_backward", prob, dprob, b, d, h, w, out)
     return out
-
-
-for _name in ("conv2d_generic", "conv2d_wgrad", "colsum", "dcn_forward_train", "dcn_backward", "dcn_backward_set",
-              "conv3x3_nhwc_acc",
-              "nearest_up2_backward_nhwc", "softmax_backward"):
-    globals()[_name] = _on_tensor_device(globals()[_name])
-del _name
 
 
 # ----------------------------------------------------------------- DTU evaluation (csrc/dtu_eval.hip)
@@ -1493,16 +1347,17 @@ def _dtu_host(values, n, name):
     return a
 
 
+@_on_tensor_device
 def dtu_cell_keys(xyz, grid):
     """tmvs_dtu_cell_keys: xyz [N,3] -> int64 [N] cell keys under grid = (origin x, y, z, cell edge)."""
     n = _dtu_xyz(xyz, "xyz")
     g = _dtu_host(grid, 4, "grid")
     keys = torch.empty(n, dtype=torch.int64, device=xyz.device)
-    with _Span("tmvs_dtu_cell_keys"):
-        _lib.check(_lib_h().tmvs_dtu_cell_keys(_ptr(xyz), n, g.ctypes.data, _ptr(keys), _stream()), "tmvs_dtu_cell_keys")
+    _launch("tmvs_dtu_cell_keys", xyz, n, g.ctypes.data, keys)
     return keys
 
 
+@_on_tensor_device
 def dtu_gather_points(xyz, order, payload=None):
     """tmvs_dtu_gather_points: float32 [N,4] records (xyz[order], int32 payload bits) in sorted order."""
     n = _dtu_xyz(xyz, "xyz")
@@ -1510,12 +1365,11 @@ def dtu_gather_points(xyz, order, payload=None):
     if payload is not None:
         _dtu_t(payload, "payload", torch.int32, (n,))
     pts = torch.empty(n, 4, dtype=torch.float32, device=xyz.device)
-    with _Span("tmvs_dtu_gather_points"):
-        _lib.check(_lib_h().tmvs_dtu_gather_points(_ptr(xyz), _ptr(order), _ptr(payload), n, _ptr(pts), _stream()),
-                   "tmvs_dtu_gather_points")
+    _launch("tmvs_dtu_gather_points", xyz, order, payload, n, pts)
     return pts
 
 
+@_on_tensor_device
 def dtu_grid_table(sorted_keys, head_rank, n_cells):
     """tmvs_dtu_grid_table: the unique keys and run starts of ascending keys, as one int64 buffer."""
     _dtu_t(sorted_keys, "sorted_keys", torch.int64)
@@ -1525,12 +1379,11 @@ def dtu_grid_table(sorted_keys, head_rank, n_cells):
     if nbytes == 0:
         raise ValueError("dtu_grid_table: n_cells must be positive")
     table = torch.empty(nbytes // 8, dtype=torch.int64, device=sorted_keys.device)
-    with _Span("tmvs_dtu_grid_table"):
-        _lib.check(_lib_h().tmvs_dtu_grid_table(_ptr(sorted_keys), _ptr(head_rank), n, int(n_cells), _ptr(table), nbytes,
-                                                _stream()), "tmvs_dtu_grid_table")
+    _launch("tmvs_dtu_grid_table", sorted_keys, head_rank, n, int(n_cells), table, nbytes)
     return table
 
 
+@_on_tensor_device
 def dtu_thin_round(points4, table, n_cells, grid, radius, state_in, state_out, undecided):
     """tmvs_dtu_thin_round: one round of the thinning; adds the points left undecided to `undecided`."""
     _dtu_t(points4, "points4", torch.float32)
@@ -1542,12 +1395,11 @@ def dtu_thin_round(points4, table, n_cells, grid, radius, state_in, state_out, u
     g = _dtu_host(grid, 4, "grid")
     if points4.dim() != 2 or points4.shape[1] != 4 or table.numel() * 8 < _lib_h().tmvs_dtu_grid_table_bytes(int(n_cells)):
         raise ValueError("dtu_thin_round: points4 must be [N, 4] and table must hold n_cells cells")
-    with _Span("tmvs_dtu_thin_round"):
-        _lib.check(_lib_h().tmvs_dtu_thin_round(_ptr(points4), n, _ptr(table), int(n_cells), g.ctypes.data,
-                                                float(radius), _ptr(state_in), _ptr(state_out), _ptr(undecided),
-                                                _stream()), "tmvs_dtu_thin_round")
+    _launch("tmvs_dtu_thin_round", points4, n, table, int(n_cells), g.ctypes.data, float(radius), state_in, state_out,
+            undecided)
 
 
+@_on_tensor_device
 def dtu_nearest_pass(from4, to4, table, n_cells, grid, bb, max_dist, block, max_ring, skip_below, d2):
     """tmvs_dtu_nearest_pass: refine d2 [N_from] float64 in place against the to-points' grid."""
     _dtu_t(from4, "from4", torch.float32)
@@ -1560,14 +1412,12 @@ def dtu_nearest_pass(from4, to4, table, n_cells, grid, bb, max_dist, block, max_
         raise ValueError("dtu_nearest_pass: table must hold n_cells cells")
     g = _dtu_host(grid, 4, "grid")
     b = _dtu_host(bb, 6, "bb")
-    with _Span("tmvs_dtu_nearest_pass"):
-        _lib.check(_lib_h().tmvs_dtu_nearest_pass(_ptr(from4), from4.shape[0], _ptr(to4), to4.shape[0], _ptr(table),
-                                                  int(n_cells), g.ctypes.data, b.ctypes.data, float(max_dist),
-                                                  float(block), int(max_ring), float(skip_below), _ptr(d2), _stream()),
-                   "tmvs_dtu_nearest_pass")
+    _launch("tmvs_dtu_nearest_pass", from4, from4.shape[0], to4, to4.shape[0], table, int(n_cells), g.ctypes.data,
+            b.ctypes.data, float(max_dist), float(block), int(max_ring), float(skip_below), d2)
     return d2
 
 
+@_on_tensor_device
 def dtu_in_mask(xyz, mask, bb_low, res):
     """tmvs_dtu_in_mask: xyz [N,3], mask uint8 [X,Y,Z] -> uint8 [N] (PointCompareMain.m:37-45)."""
     n = _dtu_xyz(xyz, "xyz")
@@ -1576,24 +1426,16 @@ def dtu_in_mask(xyz, mask, bb_low, res):
         raise ValueError("mask must be [X, Y, Z]")
     b = _dtu_host(bb_low, 3, "bb_low")
     out = torch.empty(n, dtype=torch.uint8, device=xyz.device)
-    with _Span("tmvs_dtu_in_mask"):
-        _lib.check(_lib_h().tmvs_dtu_in_mask(_ptr(xyz), n, _ptr(mask), *mask.shape, b.ctypes.data, float(res), _ptr(out),
-                                             _stream()), "tmvs_dtu_in_mask")
+    _launch("tmvs_dtu_in_mask", xyz, n, mask, *mask.shape, b.ctypes.data, float(res), out)
     return out
 
 
+@_on_tensor_device
 def dtu_above_plane(xyz, plane):
     """tmvs_dtu_above_plane: xyz [N,3], plane (4 numbers) -> uint8 [N] (PointCompareMain.m:57)."""
     n = _dtu_xyz(xyz, "xyz")
     p = _dtu_host(plane, 4, "plane")
     out = torch.empty(n, dtype=torch.uint8, device=xyz.device)
-    with _Span("tmvs_dtu_above_plane"):
-        _lib.check(_lib_h().tmvs_dtu_above_plane(_ptr(xyz), n, p.ctypes.data, _ptr(out), _stream()),
-                   "tmvs_dtu_above_plane")
+    _launch("tmvs_dtu_above_plane", xyz, n, p.ctypes.data, out)
     return out
 
-
-for _name in ("dtu_cell_keys", "dtu_gather_points", "dtu_grid_table", "dtu_thin_round", "dtu_nearest_pass", "dtu_in_mask",
-              "dtu_above_plane"):
-    globals()[_name] = _on_tensor_device(globals()[_name])
-del _name

@@ -26,7 +26,6 @@ import numpy as np
 import torch
 
 from . import data, dynamic_fusion, fusion, ops
-from ._lib import check, load
 
 CONF_THRESHOLD = 0.01  # test.py:144
 DEPTH_MIN, DEPTH_MAX = 425.0, 935.0  # test.py:156
@@ -99,12 +98,9 @@ def postprocess_view(outputs, image=None, conf_threshold=CONF_THRESHOLD, depth_m
         rgba, rgbd = res["rgba_u8"], _dev_f32(res["rgbd"], "out rgbd", (h, w, 4))
         if not rgba.is_cuda or rgba.dtype != torch.uint8 or not rgba.is_contiguous() or tuple(rgba.shape) != (h, w, 4):
             raise RuntimeError("postprocess_view: out rgba_u8 must be a contiguous uint8 CUDA tensor [H, W, 4]")
-    ptr = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(depth.device), ops._Span("tmvs_depth_postprocess"):  # the outputs' device and stream
-        check(load().tmvs_depth_postprocess(depth.data_ptr(), conf3.data_ptr(), conf2.data_ptr(), conf1.data_ptr(),
-                                            ptr(image), h, w, float(conf_threshold), float(depth_min),
-                                            float(depth_max), res["conf_final"].data_ptr(), res["depth"].data_ptr(),
-                                            ptr(rgba), ptr(rgbd), ops._stream()), "tmvs_depth_postprocess")
+    with torch.cuda.device(depth.device):  # the outputs' device and stream
+        ops._launch("tmvs_depth_postprocess", depth, conf3, conf2, conf1, image, h, w, float(conf_threshold),
+                    float(depth_min), float(depth_max), res["conf_final"], res["depth"], rgba, rgbd)
     return res
 
 
@@ -135,7 +131,6 @@ def resize_image(src, new_w, new_h, tables=None):
     if new_w <= 0 or new_h <= 0:
         raise ValueError("resize_image: the new size must be positive")
     tables = tables if tables is not None else _AxisTables(src.device)
-    lib = load()
     if src.dtype == torch.uint8:
         if src.dim() != 3 or src.shape[2] != 3:
             raise ValueError("resize_image: a uint8 source must be [h, w, 3]")
@@ -143,10 +138,7 @@ def resize_image(src, new_w, new_h, tables=None):
         x0, x1, tx = tables.get(new_w, w)
         y0, y1, ty = tables.get(new_h, h)
         dst = torch.empty(3, new_h, new_w, device=src.device)
-        with ops._Span("tmvs_resize_bilinear_u8"):
-            check(lib.tmvs_resize_bilinear_u8(src.data_ptr(), h, w, x0.data_ptr(), x1.data_ptr(), tx.data_ptr(),
-                                              y0.data_ptr(), y1.data_ptr(), ty.data_ptr(), new_h, new_w,
-                                              dst.data_ptr(), ops._stream()), "tmvs_resize_bilinear_u8")
+        ops._launch("tmvs_resize_bilinear_u8", src, h, w, x0, x1, tx, y0, y1, ty, new_h, new_w, dst)
         return dst
     if src.dtype != torch.float32 or src.dim() != 3:
         raise ValueError("resize_image: src must be uint8 [h, w, 3] or float32 [C, h, w]")
@@ -154,10 +146,7 @@ def resize_image(src, new_w, new_h, tables=None):
     x0, x1, tx = tables.get(new_w, w)
     y0, y1, ty = tables.get(new_h, h)
     dst = torch.empty(c, new_h, new_w, device=src.device)
-    with ops._Span("tmvs_resize_bilinear_f32"):
-        check(lib.tmvs_resize_bilinear_f32(src.data_ptr(), c, h, w, x0.data_ptr(), x1.data_ptr(), tx.data_ptr(),
-                                           y0.data_ptr(), y1.data_ptr(), ty.data_ptr(), new_h, new_w, dst.data_ptr(),
-                                           ops._stream()), "tmvs_resize_bilinear_f32")
+    ops._launch("tmvs_resize_bilinear_f32", src, c, h, w, x0, x1, tx, y0, y1, ty, new_h, new_w, dst)
     return dst
 
 
