@@ -1,6 +1,9 @@
 """Time tmvs_deform_conv2d at the FeatureNet head sizes (5 DTU views batched), offsets ~N(0, 1.5) px.
 HIP events on the current stream, median of 10 after 3 warm-ups. Variant via TMVS_DCN_* env.
-DCN_FUSED=1 times tmvs_dcn_fused; with DCN_SAVE=path / DCN_COMPARE=path its outputs are saved / compared bit for bit."""
+DCN_FUSED=1 times tmvs_dcn_fused; with DCN_SAVE=path / DCN_COMPARE=path its outputs are saved / compared bit for bit.
+Caveat: this script never checked values. Until the fix that tests/test_gpu_featurenet_layers.py pins, the unfused
+tmvs_deform_conv2d at these sizes (more units than workgroups) sampled each unit with the next unit's offsets and
+masks; the arithmetic was the same, so its recorded unfused timings stand. tmvs_dcn_fused was not affected."""
 import os, sys
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "."))
 import numpy as np, torch

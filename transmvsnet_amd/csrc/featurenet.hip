@@ -270,7 +270,8 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
   const float fH = (float)H, fW = (float)W;
 
   // global -> register copy of a unit's window (zeros outside the image) and (not FUSED) of the
-  // offsets/mask logits of the (tap, pixel) records this lane builds (r = lane + 64 i < 144)
+  // offsets/mask logits of the (tap, pixel) records this lane builds (r = lane + 64 i < 144); the loop
+  // moves a unit's logits from omv to omc before it prefetches the next unit's
   floatx4_t stg[Cfg::STAGE];
   float omv[9];
   auto fetch = [&](int u) {
@@ -311,6 +312,14 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
       if (Cfg::WIN4 % NT == 0 || idx < Cfg::WIN4) win[dcn_slot(idx >> 3, idx & 7)] = stg[i];
     }
     __syncthreads();
+    // not FUSED: fetch() also loads the next unit's offset/mask logits into omv, so this unit's move out of
+    // its way first (FUSED recomputes omv from the window after the prefetch)
+    float omc[9];
+    if (!FUSED) {
+#pragma unroll
+      for (int i = 0; i < 9; ++i) omc[i] = omv[i];
+    }
+    const float(&omu)[9] = FUSED ? omv : omc;
     if (u + 1 < u_end) fetch(u + 1);  // next window in flight during this unit's work
     const int row = band * NW + wv;
     const int x0t = xs * dcn::TW, nvalid = min(dcn::TW, W - x0t);
@@ -387,8 +396,8 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
       const int r = lane + 64 * i;
       if (r < dcn::NREC) {
         const int tap = r >> 4, px = r & 15, ki = tap / 3, kj = tap - 3 * ki;
-        const float py = (float)(row + ki - 1) + omv[3 * i + 0];
-        const float pxf = (float)(x0t + min(px, nvalid - 1) + kj - 1) + omv[3 * i + 1];
+        const float py = (float)(row + ki - 1) + omu[3 * i + 0];
+        const float pxf = (float)(x0t + min(px, nvalid - 1) + kj - 1) + omu[3 * i + 1];
         const bool inside = py > -1.f && py < fH && pxf > -1.f && pxf < fW;
         const float y0 = floorf(py), x0 = floorf(pxf);
         const float ly = py - y0, lx = pxf - x0;
@@ -397,7 +406,7 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
         const int ry = y0i - wy0, rxw = x0i - wx0;
         const bool inwin = (unsigned)ry < (unsigned)(Cfg::WR - 1) && (unsigned)rxw < (unsigned)(Cfg::WC - 1);
         lane_fast = lane_fast && (inwin || !inside);
-        const float mk = __frcp_rn(1.f + __expf(-omv[3 * i + 2]));  // sigmoid (fast exp / rcp)
+        const float mk = __frcp_rn(1.f + __expf(-omu[3 * i + 2]));  // sigmoid (fast exp / rcp)
         // inside => y0 in [-1, H-1], x0 in [-1, W-1]: the fallback code fits 30 bits
         const int code = !inside ? 0 : inwin ? ry * Cfg::WC + rxw : -1 - (((y0i + 1) << 15) | (x0i + 1));
         (void)hy;
