@@ -7,9 +7,9 @@ window and one past it, exactly on the image border, far past the offset clamp, 
 steady-state walk of the persistent kernels (a workgroup computing on a unit that fetch() staged during the
 walk, not before it).
 
-  tmvs_deform_conv2d       dcn_window_kernel<CO, false, 12, 3>   unit 12 rows x 16 pixels, halo 3, persistent
-  tmvs_dcn_fused           dcn_window_kernel<CO, true, 12, 3>
-  tmvs_dcn_forward_train   dcn_window_kernel<CO, true, 12, 3> with offset_mask_out
+  tmvs_deform_conv2d       dcn_window_kernel<CO, false>          unit 12 rows x 16 pixels, halo 3, persistent
+  tmvs_dcn_fused           dcn_window_kernel<CO, true>
+  tmvs_dcn_forward_train   dcn_window_kernel<CO, true> with offset_mask_out
   tmvs_conv3x3_nhwc(_acc)  conv3x3_window_kernel                 unit 8 x 16, halo 1, persistent
   tmvs_conv2d_bn_relu      conv2d_bn_relu_kernel, 7 instances    unit 8 x 16 output pixels, persistent
   tmvs_fpn_merge           fpn_merge_kernel<8 / 16>              4 lanes per pixel, 64 pixels per block

@@ -12,10 +12,9 @@
 // Work unit = (image, 8 output rows, 16 output columns): wave w of the 512-thread block owns output
 // row 8*band + w. Per unit the block stages the input window (rows 7S+K, columns 15S+K, zeros
 // outside the image) in LDS; the next unit's window is loaded into registers during this unit's
-// MFMAs (persistent grid, XCD-contiguous unit ranges) -- the DCN kernels' scheme (featurenet.hip).
-#include "common.h"
-
-#include <algorithm>
+// MFMAs (persistent grid, XCD-contiguous unit ranges): the window scheme of window_conv.h, shared with
+// the DCN and 3x3 kernels of featurenet.hip: the window layout and the persistent grid come from there.
+#include "window_conv.h"
 
 namespace tmvs {
 
@@ -26,18 +25,11 @@ struct Conv2dCfg {
   static constexpr int MT = (CO + 15) / 16;
   static constexpr int NIDX = K * K * G;       // (tap, chunk) pairs
   static constexpr int NB = (NIDX + 3) / 4;    // k-blocks
-  static constexpr int WR = 7 * S + K, WC = 15 * S + K, WP = WR * WC;
-  static constexpr int WIN4 = WP * G;
-  static constexpr int STAGE = (WIN4 + 511) / 512;
   static constexpr int PAD = K / 2;
   static constexpr int SH = G == 8 ? 0 : G == 4 ? 2 : 3;  // chunk swizzle: c ^ ((P >> SH) & (G - 1))
+  using Win = wconv::Window<G, SH, 7 * S + K, 15 * S + K, 512>;  // the input window of 8 x 16 outputs
   static constexpr int NA4 = NB * MT * 64;
 };
-
-template <int G, int SH>
-__device__ __forceinline__ int c2_slot(int P, int c) {
-  return G == 1 ? P : P * G + (c ^ ((P >> SH) & (G - 1)));
-}
 
 template <int CI, int CO, int K, int S, bool NCHW>
 __global__ __launch_bounds__(512) void conv2d_bn_relu_kernel(const float* __restrict__ x, const float* __restrict__ wpk,
@@ -45,8 +37,9 @@ __global__ __launch_bounds__(512) void conv2d_bn_relu_kernel(const float* __rest
                                                              const float* __restrict__ shift, int relu, int B, int H,
                                                              int W, int Ho, int Wo, float* __restrict__ out) {
   using C = Conv2dCfg<CI, CO, K, S, NCHW>;
+  using Win = typename C::Win;
   __shared__ floatx4_t wl[C::NA4];
-  __shared__ floatx4_t win[C::WIN4];
+  __shared__ floatx4_t win[Win::WIN4];
   // BN alpha / shift in LDS for the epilogue (from global there, each was a serialised L2 round trip per unit)
   __shared__ __attribute__((aligned(16))) float cst[2][C::MT * 16];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -61,15 +54,15 @@ __global__ __launch_bounds__(512) void conv2d_bn_relu_kernel(const float* __rest
   const int u_end = (int)((long long)nunits * (bid + 1) / gridDim.x);
   const int j = lane >> 4, n = lane & 15;
   const size_t img = (size_t)H * W * (NCHW ? CI : C::CIP);
-  floatx4_t stg[C::STAGE];
+  floatx4_t stg[Win::STAGE];
   auto fetch = [&](int u) {
     const int b = u / (nby * nbx), rem = u - b * (nby * nbx), band = rem / nbx, xs = rem - band * nbx;
     const int iy0 = band * 8 * S - C::PAD, ix0 = xs * 16 * S - C::PAD;
     const __amdgpu_buffer_rsrc_t rx = raw_rsrc(x + b * img, (unsigned)(img * 4));
 #pragma unroll
-    for (int i = 0; i < C::STAGE; ++i) {
-      const int idx = min(tid + 512 * i, C::WIN4 - 1), pix = idx / C::G, ch = idx - pix * C::G;
-      const int r = pix / C::WC, c = pix - r * C::WC;
+    for (int i = 0; i < Win::STAGE; ++i) {
+      const int idx = min(tid + 512 * i, Win::WIN4 - 1), pix = idx / C::G, ch = idx - pix * C::G;
+      const int r = pix / Win::WC, c = pix - r * Win::WC;
       const int gy = iy0 + r, gx = ix0 + c;
       const bool ok = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
       if (NCHW) {  // CI = 3 planes -> (c0, c1, c2, 0)
@@ -87,11 +80,11 @@ __global__ __launch_bounds__(512) void conv2d_bn_relu_kernel(const float* __rest
     const int b = u / (nby * nbx), rem = u - b * (nby * nbx), band = rem / nbx, xs = rem - band * nbx;
     __syncthreads();  // previous unit's window reads done (first time: weights staged)
 #pragma unroll
-    for (int i = 0; i < C::STAGE; ++i) {
+    for (int i = 0; i < Win::STAGE; ++i) {
       const int idx = tid + 512 * i;
-      if (idx < C::WIN4) {
+      if (idx < Win::WIN4) {
         const int pix = idx / C::G;
-        win[c2_slot<C::G, C::SH>(pix, idx - pix * C::G)] = stg[i];
+        win[Win::slot(pix, idx - pix * C::G)] = stg[i];
       }
     }
     __syncthreads();
@@ -106,8 +99,8 @@ __global__ __launch_bounds__(512) void conv2d_bn_relu_kernel(const float* __rest
     auto frag = [&](int kb, int bf) {
       const int idx = min(4 * kb + j, C::NIDX - 1);  // padded pairs carry zero weights
       const int tap = idx / C::G, ch = idx - tap * C::G, ki = tap / K, kj = tap - ki * K;
-      const int P = (wv * S + ki) * C::WC + n * S + kj;
-      fb[bf] = win[c2_slot<C::G, C::SH>(P, ch)];
+      const int P = (wv * S + ki) * Win::WC + n * S + kj;
+      fb[bf] = win[Win::slot(P, ch)];
 #pragma unroll
       for (int m = 0; m < C::MT; ++m) fa[bf][m] = wl[(kb * C::MT + m) * 64 + lane];
     };
@@ -148,24 +141,17 @@ __global__ __launch_bounds__(512) void conv2d_bn_relu_kernel(const float* __rest
 template <int CI, int CO, int K, int S, bool NCHW>
 static int conv2d_launch(const float* x, const float* w, const float* alpha, const float* shift, int relu, int B,
                          int H, int W, float* out, hipStream_t st) {
-  static int grid = 0;
-  if (!grid) {
-    int dev = 0, ncu = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return TMVS_ERR_HIP;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv2d_bn_relu_kernel<CI, CO, K, S, NCHW>, 512, 0);
-    grid = std::max(1, ncu * std::max(occ, 1));
-  }
   const int pad = K / 2, Ho = (H + 2 * pad - K) / S + 1, Wo = (W + 2 * pad - K) / S + 1;
   const long long nunits = (long long)B * ((Ho + 7) / 8) * ((Wo + 15) / 16);
-  const int nblk = (int)std::min<long long>(grid, nunits);
+  const int nblk = wconv::persistent_blocks<conv2d_bn_relu_kernel<CI, CO, K, S, NCHW>>(512, nunits);
+  if (!nblk) return TMVS_ERR_HIP;
   hipLaunchKernelGGL((conv2d_bn_relu_kernel<CI, CO, K, S, NCHW>), dim3(nblk), dim3(512), 0, st, x, w, alpha, shift,
                      relu, B, H, W, Ho, Wo, out);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
 }
 
-// the FeatureNet layer shapes: (cin, cout, k, stride); cin = 3 reads the NCHW image
+// the FeatureNet layer shapes: (cin, cout, k, stride); cin = 3 reads the NCHW image. Any other: TMVS_ERR_SHAPE
 static int conv2d_dispatch(int cin, int cout, int k, int s, const float* x, const float* w, const float* a,
                            const float* sh, int relu, int B, int H, int W, float* out, hipStream_t st) {
 #define TMVS_C2D(CI, CO, K, S, NC) \
@@ -179,13 +165,6 @@ static int conv2d_dispatch(int cin, int cout, int k, int s, const float* x, cons
   TMVS_C2D(32, 32, 1, 1, false);
 #undef TMVS_C2D
   return TMVS_ERR_SHAPE;
-}
-
-static bool conv2d_supported(int cin, int cout, int k, int s) {
-  return (cin == 3 && cout == 8 && k == 3 && s == 1) || (cin == 8 && cout == 8 && k == 3 && s == 1) ||
-         (cin == 8 && cout == 16 && k == 5 && s == 2) || (cin == 16 && cout == 16 && k == 3 && s == 1) ||
-         (cin == 16 && cout == 32 && k == 5 && s == 2) || (cin == 32 && cout == 32 && k == 3 && s == 1) ||
-         (cin == 32 && cout == 32 && k == 1 && s == 1);
 }
 
 }  // namespace tmvs
@@ -224,7 +203,6 @@ extern "C" int tmvs_conv2d_bn_relu(const float* x, int batch, int cin, int heigh
                                    float* out_nhwc, void* stream) {
   if (!x || !w_packed || !out_nhwc || batch <= 0 || height <= 0 || width <= 0) return TMVS_ERR_ARG;
   if ((bn_alpha == nullptr) != (bn_shift == nullptr)) return TMVS_ERR_ARG;
-  if (!conv2d_supported(cin, cout, k, stride)) return TMVS_ERR_SHAPE;
   if ((long long)height * width * (cin < 4 ? 4 : cin) * 4 >= (1LL << 31)) return TMVS_ERR_SHAPE;
   return conv2d_dispatch(cin, cout, k, stride, x, w_packed, bn_alpha, bn_shift, relu, batch, height, width, out_nhwc,
                          (hipStream_t)stream);

@@ -1,6 +1,6 @@
 // FeatureNet heads (models/module.py:362-395): the modulated deformable convolution DCNv2
 // (models/dcn.py:66-80 -> torchvision.ops.deform_conv2d, torchvision 0.10.1) with the head's
-// bias / BatchNorm / ReLU fused into the epilogue.
+// bias / BatchNorm / ReLU fused into the epilogue, the heads' 3x3 conv, and the FPN merge.
 //
 // deform_conv2d, stride 1, padding 1, dilation 1, one offset group, 3x3 taps k = 3i + j:
 //   (py, px) = (y + i - 1 + om[2k], x + j - 1 + om[2k+1]),   mask_k = sigmoid(om[18 + k])
@@ -15,115 +15,92 @@
 // pixel n itself and holds channels {4j..4j+3} (k-steps 0-3) and {16+4j..16+4j+3} (k-steps 4-7)
 // of the tap: the weights are packed in that K order, as the kernel's LDS image.
 //
-// Work unit = (image, NW-row band, 16-pixel column step); wave w of the NW*64-thread block owns row
-// NW*band + w of the unit (NW = 12 by default: 3 waves/SIMD). Per unit the block stages the source
-// window rows [NW*band - HL, +NW+2HL) x columns [x0 - HL, +16+2HL) x 32 channels in LDS (HL = 3:
-// 50 KB), so the 4 bilinear corners of every tap whose offsets stay within the window (|offset| up to
-// ~HL - 1 px; the reference's zero-initialised offsets, models/dcn.py:62-64, always) are LDS reads; a
-// wave whose unit has a sample beyond the window runs the same taps with per-lane global fallback
-// gathers (dcn_taps_slow). The next unit's window is fetched into registers during the current unit's
-// taps. Window layout: 16-byte chunk c of window pixel P at P*8 + (c ^ (P & 7)), which makes both the
-// staging writes (one 128-byte pixel row per 8 lanes) and the B-layout reads (chunks j and j+4 of 16
-// pixels per lane group) bank-conflict-free. Per (tap, pixel) 16-byte sampling records (the bilinear
-// fractions, window index, mask) are built once per unit and shared by the 4 lanes of a pixel.
-#include "common.h"
-
-#include <algorithm>
+// Both window kernels here take their window layout (sizes, slot swizzle) and their persistent grid from
+// window_conv.h; the rest of the scheme is spelled out in each (profiles/featurenet_scaffold_resources.md).
+// The DCN's work unit = (image, 12-row band, 16-pixel column step); wave w of the 768-thread block
+// (3 waves/SIMD) owns row 12 band + w. Its window is rows [12 band - 3, +18) x columns [x0 - 3, +22) x
+// 32 channels (50 KB), so the 4 bilinear corners of every tap whose offsets stay within the window
+// (|offset| up to ~2 px; the reference's zero-initialised offsets, models/dcn.py:62-64, always) are LDS
+// reads (dcn_taps); a wave whose unit has a sample beyond the window runs the same taps one at a time
+// with per-lane global fallback gathers (dcn_taps_slow). Per (tap, pixel) 16-byte sampling records (the
+// bilinear fractions, window index, mask) are built once per unit and shared by the 4 lanes of a pixel.
+#include "window_conv.h"
 
 namespace tmvs {
 
 namespace dcn {
 constexpr int CI = 32;     // input channels (FeatureNet heads: 4 * base_channels)
-constexpr int WAVES = 8;   // waves per block = rows per unit (the 3x3 conv's unit; the DCN's: DcnWin)
 constexpr int TW = 16;     // pixels per wave row
 constexpr int NREC = 9 * TW;                               // (tap, pixel) records per wave
+// The DCN's unit: WAVES waves = rows of 16 pixels (3 waves/SIMD), a window margin of HALO pixels on every
+// side (samples whose 4 corners stay inside it read LDS; others take the global path)
+constexpr int WAVES = 12, HALO = 3, NT = WAVES * 64;
+using Win = wconv::Window<8, 0, WAVES + 2 * HALO, TW + 2 * HALO, NT>;
+constexpr int WR = Win::WR, WC = Win::WC;                  // window rows, columns
+constexpr int WIN4 = Win::WIN4, STAGE = Win::STAGE;        // window float4s; float4 per thread per window copy
 }  // namespace dcn
-
-// The DCN's unit / window geometry: NW waves = NW rows of 16 pixels per unit, a window margin of HL
-// pixels on every side (samples whose 4 corners stay inside it read LDS; others take the global path)
-template <int NW, int HL>
-struct DcnWin {
-  static constexpr int WAVES = NW, HALO = HL, NT = NW * 64;
-  static constexpr int WR = NW + 2 * HL, WC = dcn::TW + 2 * HL;  // window rows, columns
-  static constexpr int WIN4 = WR * WC * 8;                       // window float4s (8 per pixel)
-  static constexpr int STAGE = (WIN4 + NT - 1) / NT;             // float4 per thread per window copy
-};
 
 typedef float float2_t __attribute__((ext_vector_type(2)));
 
-// Window slot of chunk c of window pixel P.
-__device__ __forceinline__ int dcn_slot(int P, int c) { return P * 8 + (c ^ (P & 7)); }
+// Window slot of chunk c of window pixel P (the DCN's and the 3x3 conv's windows: 8 chunks per pixel).
+__device__ __forceinline__ int dcn_slot(int P, int c) { return dcn::Win::slot(P, c); }
 
-// The 9 taps of one wave-unit: gather (window LDS; beyond it, global, unless FAST), blend,
-// modulate, MT x 8 MFMAs per tap.
-// SB: one gather / A-fragment buffer (a tap's blend consumes the gathers before the next tap's refill
-// them; the next tap's A fragments are read after this tap's MFMAs): the register budget of 3 waves/SIMD
-template <int MT, bool FAST, int WC, bool SB = false>
+// The 9 taps of one wave-unit whose samples all stay inside the window: gather from the window, blend,
+// modulate, MT x 8 MFMAs per tap. One gather / A-fragment buffer (a tap's blend consumes the gathers
+// before the next tap's refill them; the next tap's A fragments are read after this tap's MFMAs): the
+// register budget of 3 waves/SIMD
+template <int MT>
 __device__ __forceinline__ void dcn_taps(floatx4_t (&acc)[MT], const floatx4_t* __restrict__ wl,
                                          const floatx4_t* __restrict__ win, const floatx4_t* __restrict__ recs,
-                                         __amdgpu_buffer_rsrc_t rx, int H, int W, int lane) {
+                                         int lane) {
   const int j = lane >> 4, n = lane & 15;
   floatx4_t alt = floatx4_t{0.f, 0.f, 0.f, 0.f};
-  constexpr int NB = SB ? 1 : 2;
-  floatx4_t v[NB][4][2], w4[NB];
-  float mk[NB];
+  floatx4_t v[4][2], w4;
+  float mk;
   // the records of the next tap to gather, read one tap before its gathers (their addresses come from
   // them: read just before, each tap had waited out an LDS round trip between its MFMA blocks)
   // record = (ly, lx, window pixel of corner (y0, x0) | fallback code, mask); a sample outside the
   // image has ly = lx = 0 and mask 0, so its B operand is 0
   floatx4_t rw;
   auto rec = [&](int k) { rw = recs[k * dcn::TW + n]; };
-  // gathers of the tap whose record is in rw into buffer bb (issued one tap ahead of their use); the
-  // bilinear weights are formed here from the fractions, the same products the record builder formed
-  auto gather = [&](int bb) {
+  // gathers of the tap whose record is in rw (issued one tap ahead of their use); the bilinear weights
+  // are formed here from the fractions, the same products the record builder formed
+  auto gather = [&]() {
     {
       const float ly = rw[0], lx = rw[1], hy = 1.f - ly, hx = 1.f - lx;
-      w4[bb] = floatx4_t{hy * hx, hy * lx, ly * hx, ly * lx};
+      w4 = floatx4_t{hy * hx, hy * lx, ly * hx, ly * lx};
     }
-    const int2 bm = make_int2(__float_as_int(rw[2]), 0);
-    mk[bb] = rw[3];
-    if (FAST || bm.x >= 0) {
+    const int P = __float_as_int(rw[2]);
+    mk = rw[3];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int Pc = bm.x + (c >> 1) * WC + (c & 1);
-        v[bb][c][0] = win[dcn_slot(Pc, j)];
-        v[bb][c][1] = win[dcn_slot(Pc, j + 4)];
-      }
-    } else {  // sample beyond the window: global gather (corners outside the image read 0)
-      const int code = -1 - bm.x, y0 = (code >> 15) - 1, x0 = (code & 32767) - 1;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int cy = y0 + (c >> 1), cx = x0 + (c & 1);
-        const bool ok = (unsigned)cy < (unsigned)H && (unsigned)cx < (unsigned)W;
-        const unsigned off = ok ? ((unsigned)(cy * W + cx) * dcn::CI + 4u * j) * 4u : kOffOut;
-        v[bb][c][0] = buf_load_f32x4(rx, off);
-        v[bb][c][1] = buf_load_f32x4(rx, off == kOffOut ? kOffOut : off + 64u);
-      }
+    for (int c = 0; c < 4; ++c) {
+      const int Pc = P + (c >> 1) * dcn::WC + (c & 1);
+      v[c][0] = win[dcn_slot(Pc, j)];
+      v[c][1] = win[dcn_slot(Pc, j + 4)];
     }
   };
-  // A fragments of tap k into buffer ab, read one tap ahead too: in LDS order they then precede the
-  // tap's gathers, so the MFMAs never wait on the gathers issued just before them
-  floatx4_t af[NB][MT][2];
-  auto lda = [&](int k, int ab) {
+  // A fragments of tap k, read after the previous tap's MFMAs
+  floatx4_t af[MT][2];
+  auto lda = [&](int k) {
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
-      af[ab][m][0] = wl[((k * MT + m) * 2 + 0) * 64 + lane];
-      af[ab][m][1] = wl[((k * MT + m) * 2 + 1) * 64 + lane];
+      af[m][0] = wl[((k * MT + m) * 2 + 0) * 64 + lane];
+      af[m][1] = wl[((k * MT + m) * 2 + 1) * 64 + lane];
     }
   };
-  // bilinear blend and modulation of the gathers in buffer bb into the tap's B operands
-  auto blend = [&](int bb, float (&b)[8]) {
+  // bilinear blend and modulation of the gathers into the tap's B operands
+  auto blend = [&](float (&b)[8]) {
     // two channels per packed fp32 instruction (v_pk_mul_f32 / v_pk_add_f32: the same IEEE operations
     // per element as the scalar form, half the VALU issue)
 #pragma unroll
     for (int e = 0; e < 8; e += 2) {
-      auto pr = [&](int c) { return float2_t{v[bb][c][e >> 2][e & 3], v[bb][c][e >> 2][(e & 3) + 1]}; };
+      auto pr = [&](int c) { return float2_t{v[c][e >> 2][e & 3], v[c][e >> 2][(e & 3) + 1]}; };
       auto bc = [](float t) { return float2_t{t, t}; };
-      float2_t val = bc(w4[bb][0]) * pr(0);
-      val = val + bc(w4[bb][1]) * pr(1);
-      val = val + bc(w4[bb][2]) * pr(2);
-      val = val + bc(w4[bb][3]) * pr(3);
-      const float2_t r = bc(mk[bb]) * val;
+      float2_t val = bc(w4[0]) * pr(0);
+      val = val + bc(w4[1]) * pr(1);
+      val = val + bc(w4[2]) * pr(2);
+      val = val + bc(w4[3]) * pr(3);
+      const float2_t r = bc(mk) * val;
       b[e] = r.x;
       b[e + 1] = r.y;
     }
@@ -140,23 +117,21 @@ __device__ __forceinline__ void dcn_taps(floatx4_t (&acc)[MT], const floatx4_t* 
       }
   };
   rec(0);
-  lda(0, 0);
-  gather(0);
+  lda(0);
+  gather();
   rec(1);
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
-    const int bb = SB ? 0 : k & 1;
     float b[8];
-    blend(bb, b);
+    blend(b);
     if (k < 8) {
-      if (!SB) lda(k + 1, bb ^ 1);
-      gather(SB ? 0 : bb ^ 1);
+      gather();
       if (k < 7) rec(k + 2);
     }
     __builtin_amdgcn_sched_barrier(0);
-    mfmas(af[bb], b);
+    mfmas(af, b);
     __builtin_amdgcn_sched_barrier(0);
-    if (SB && k < 8) lda(k + 1, 0);
+    if (k < 8) lda(k + 1);
   }
   if (MT == 1) acc[0] = acc[0] + alt;
 }
@@ -164,7 +139,7 @@ __device__ __forceinline__ void dcn_taps(floatx4_t (&acc)[MT], const floatx4_t* 
 // The taps of a wave-unit with a sample beyond the window (rare: offsets over ~HALO - 1 px), in the
 // simplest form -- one tap at a time, no read-ahead -- so it does not raise the kernel's register
 // budget: the same gathers (window or global), blend and MFMA chains as dcn_taps, so the same results.
-template <int MT, int WC>
+template <int MT>
 __device__ __forceinline__ void dcn_taps_slow(floatx4_t (&acc)[MT], const floatx4_t* __restrict__ wl,
                                            const floatx4_t* __restrict__ win, const floatx4_t* __restrict__ recs,
                                            __amdgpu_buffer_rsrc_t rx, int H, int W, int lane) {
@@ -181,7 +156,7 @@ __device__ __forceinline__ void dcn_taps_slow(floatx4_t (&acc)[MT], const floatx
     if (code >= 0) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const int Pc = code + (c >> 1) * WC + (c & 1);
+        const int Pc = code + (c >> 1) * dcn::WC + (c & 1);
         v[c][0] = win[dcn_slot(Pc, j)];
         v[c][1] = win[dcn_slot(Pc, j + 4)];
       }
@@ -228,8 +203,8 @@ __device__ __forceinline__ void dcn_taps_slow(floatx4_t (&acc)[MT], const floatx
 // FUSED: the DCN's offset/mask conv (conv_offset_mask, models/dcn.py:58-64: 3x3, 32 -> 27, bias)
 // is computed in-kernel from the same LDS window (implicit GEMM on MFMA, M = 27 padded to 32), so
 // the [27][H][W] offset/mask tensor never exists in HBM; otherwise `om` is read from global.
-template <int CO, bool FUSED, int NW, int HL>
-__global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __restrict__ x, const float* __restrict__ om,
+template <int CO, bool FUSED>
+__global__ __launch_bounds__(dcn::NT) void dcn_window_kernel(const float* __restrict__ x, const float* __restrict__ om,
                                                          const float* __restrict__ wom, const float* __restrict__ bom,
                                                          const float* __restrict__ wpk,
                                                          const float* __restrict__ bias,
@@ -238,14 +213,13 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
                                                          int W, float* __restrict__ out,
                                                          float* __restrict__ out_nhwc,
                                                          float* __restrict__ om_out) {
-  using Cfg = DcnWin<NW, HL>;
-  constexpr int NT = Cfg::NT;
+  constexpr int NW = dcn::WAVES, HL = dcn::HALO, NT = dcn::NT;
   constexpr int MT = (CO + 15) / 16;
   constexpr int NA4 = 9 * MT * 2 * 64;  // A fragments [tap][mt][half][lane] float4
   constexpr int NO4 = FUSED ? 9 * 2 * 2 * 64 : 1;  // offset-conv A fragments (27 rows padded to 32)
   __shared__ floatx4_t wl[NA4];
   __shared__ floatx4_t wo[NO4];
-  __shared__ floatx4_t win[Cfg::WIN4];                  // swizzled [row][col] pixels of 8 chunks
+  __shared__ floatx4_t win[dcn::WIN4];                  // swizzled [row][col] pixels of 8 chunks
   __shared__ floatx4_t recs[NW][dcn::NREC];             // [tap][px] sampling records (16 B)
                                                         // (FUSED: first the [px][33] offset/mask tile)
   // per-channel constants: bias, BN alpha, BN shift (CO), offset-conv bias (27): read from LDS in the
@@ -272,16 +246,16 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
   // global -> register copy of a unit's window (zeros outside the image) and (not FUSED) of the
   // offsets/mask logits of the (tap, pixel) records this lane builds (r = lane + 64 i < 144); the loop
   // moves a unit's logits from omv to omc before it prefetches the next unit's
-  floatx4_t stg[Cfg::STAGE];
+  floatx4_t stg[dcn::STAGE];
   float omv[9];
   auto fetch = [&](int u) {
     const int b = u / (nby * nbx), rem = u - b * (nby * nbx), band = rem / nbx, xs = rem - band * nbx;
     const int wy0 = band * NW - HL, wx0 = xs * dcn::TW - HL;
     const __amdgpu_buffer_rsrc_t rx = raw_rsrc(x + (size_t)b * HW * dcn::CI, (unsigned)HW * dcn::CI * 4);
 #pragma unroll
-    for (int i = 0; i < Cfg::STAGE; ++i) {
-      const int idx = min(tid + NT * i, Cfg::WIN4 - 1), pix = idx >> 3, ch = idx & 7;
-      const int r = pix / Cfg::WC, c = pix - r * Cfg::WC;
+    for (int i = 0; i < dcn::STAGE; ++i) {
+      const int idx = min(tid + NT * i, dcn::WIN4 - 1), pix = idx >> 3, ch = idx & 7;
+      const int r = pix / dcn::WC, c = pix - r * dcn::WC;
       const int gy = wy0 + r, gx = wx0 + c;
       const bool ok = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
       stg[i] = buf_load_f32x4(rx, ok ? ((unsigned)(gy * W + gx) * dcn::CI + 4u * ch) * 4u : kOffOut);
@@ -307,9 +281,9 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
     const int wy0 = band * NW - HL, wx0 = xs * dcn::TW - HL;
     __syncthreads();  // previous unit's window reads are done (and, first time, the weights are staged)
 #pragma unroll
-    for (int i = 0; i < Cfg::STAGE; ++i) {
+    for (int i = 0; i < dcn::STAGE; ++i) {
       const int idx = tid + NT * i;
-      if (Cfg::WIN4 % NT == 0 || idx < Cfg::WIN4) win[dcn_slot(idx >> 3, idx & 7)] = stg[i];
+      if (dcn::WIN4 % NT == 0 || idx < dcn::WIN4) win[dcn_slot(idx >> 3, idx & 7)] = stg[i];
     }
     __syncthreads();
     // not FUSED: fetch() also loads the next unit's offset/mask logits into omv, so this unit's move out of
@@ -327,32 +301,26 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
     if (FUSED) {
       // conv_offset_mask of this wave's 16 pixels from the window: B lane (j, n) = chunks j, j+4 of
       // window pixel (wv + HALO + ki - 1, HALO + n + kj - 1); D lane (j, n) = channels 16m + 4j + i
-      // (tap k + 1's fragments are read during tap k's MFMAs)
       floatx4_t ao[2] = {floatx4_t{0.f, 0.f, 0.f, 0.f}, floatx4_t{0.f, 0.f, 0.f, 0.f}};
-      constexpr int OB = NW > 8 ? 1 : 2;  // 3 waves/SIMD: one buffer, each tap's fragments read just before it
-      floatx4_t fb[OB][2], fa[OB][2][2];
-      auto frag = [&](int k, int bf) {
+      // (one buffer, each tap's fragments read just before it: the register budget of 3 waves/SIMD)
+      floatx4_t fb[2], fa[2][2];
+      auto frag = [&](int k) {
         const int ki = k / 3, kj = k - 3 * ki;
-        const int P = (wv + HL + ki - 1) * Cfg::WC + HL + n + kj - 1;
-        fb[bf][0] = win[dcn_slot(P, j)];
-        fb[bf][1] = win[dcn_slot(P, j + 4)];
+        const int P = (wv + HL + ki - 1) * dcn::WC + HL + n + kj - 1;
+        fb[0] = win[dcn_slot(P, j)];
+        fb[1] = win[dcn_slot(P, j + 4)];
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-          fa[bf][m][0] = wo[((k * 2 + m) * 2 + 0) * 64 + lane];
-          fa[bf][m][1] = wo[((k * 2 + m) * 2 + 1) * 64 + lane];
+          fa[m][0] = wo[((k * 2 + m) * 2 + 0) * 64 + lane];
+          fa[m][1] = wo[((k * 2 + m) * 2 + 1) * 64 + lane];
         }
       };
-      if (OB == 2) frag(0, 0);
 #pragma unroll
       for (int k = 0; k < 9; ++k) {
-        if (OB == 1)
-          frag(k, 0);
-        else if (k < 8)
-          frag(k + 1, (k + 1) & 1);
+        frag(k);
         __builtin_amdgcn_sched_barrier(0);  // keep those reads ahead of this tap's MFMAs
-        const int ob = OB == 1 ? 0 : k & 1;
-        const floatx4_t b0 = fb[ob][0], b1 = fb[ob][1];
-        const floatx4_t(&a)[2][2] = fa[ob];
+        const floatx4_t b0 = fb[0], b1 = fb[1];
+        const floatx4_t(&a)[2][2] = fa;
 #pragma unroll
         for (int s = 0; s < 8; ++s)
 #pragma unroll
@@ -401,16 +369,13 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
         const bool inside = py > -1.f && py < fH && pxf > -1.f && pxf < fW;
         const float y0 = floorf(py), x0 = floorf(pxf);
         const float ly = py - y0, lx = pxf - x0;
-        const float hy = 1.f - ly, hx = 1.f - lx;
         const int y0i = (int)fmaxf(fminf(y0, 32766.f), -2.f), x0i = (int)fmaxf(fminf(x0, 32766.f), -2.f);
         const int ry = y0i - wy0, rxw = x0i - wx0;
-        const bool inwin = (unsigned)ry < (unsigned)(Cfg::WR - 1) && (unsigned)rxw < (unsigned)(Cfg::WC - 1);
+        const bool inwin = (unsigned)ry < (unsigned)(dcn::WR - 1) && (unsigned)rxw < (unsigned)(dcn::WC - 1);
         lane_fast = lane_fast && (inwin || !inside);
         const float mk = __frcp_rn(1.f + __expf(-omu[3 * i + 2]));  // sigmoid (fast exp / rcp)
         // inside => y0 in [-1, H-1], x0 in [-1, W-1]: the fallback code fits 30 bits
-        const int code = !inside ? 0 : inwin ? ry * Cfg::WC + rxw : -1 - (((y0i + 1) << 15) | (x0i + 1));
-        (void)hy;
-        (void)hx;
+        const int code = !inside ? 0 : inwin ? ry * dcn::WC + rxw : -1 - (((y0i + 1) << 15) | (x0i + 1));
         recs[wv][r] = inside ? floatx4_t{ly, lx, __int_as_float(code), mk} : floatx4_t{0.f, 0.f, __int_as_float(0), 0.f};
       }
     }
@@ -420,13 +385,10 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
     floatx4_t acc[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = floatx4_t{0.f, 0.f, 0.f, 0.f};
-    constexpr bool SB = NW > 8;  // 3 waves/SIMD: single buffers
     if (fast)
-      dcn_taps<MT, true, Cfg::WC, SB>(acc, wl, win, recs[wv], rx, H, W, lane);
-    else if (SB)
-      dcn_taps_slow<MT, Cfg::WC>(acc, wl, win, recs[wv], rx, H, W, lane);
+      dcn_taps<MT>(acc, wl, win, recs[wv], lane);
     else
-      dcn_taps<MT, false, Cfg::WC, SB>(acc, wl, win, recs[wv], rx, H, W, lane);
+      dcn_taps_slow<MT>(acc, wl, win, recs[wv], rx, H, W, lane);
     // D fragment: lane (j, n) holds output channels 16m + 4j .. +3 of pixel (row, x0t + n)
     if (n < nvalid) {
       const int pq = row * W + x0t + n;
@@ -459,10 +421,10 @@ __global__ __launch_bounds__(NW * 64) void dcn_window_kernel(const float* __rest
 // blocks per CU) and its B-layout window reads feeding MFMA directly (the weights packed as a DCN
 // weight). Output NHWC (the next DCN's input) and optionally NCHW.
 namespace c3 {
+constexpr int WAVES = 8;  // waves per block = rows per unit
 constexpr int HALO = 1;
-constexpr int WR = dcn::WAVES + 2 * HALO, WC = dcn::TW + 2 * HALO;
-constexpr int WIN4 = WR * WC * 8;
-constexpr int STAGE = (WIN4 + 511) / 512;
+using Win = wconv::Window<8, 0, WAVES + 2 * HALO, dcn::TW + 2 * HALO, WAVES * 64>;
+constexpr int WC = Win::WC, WIN4 = Win::WIN4, STAGE = Win::STAGE;
 }  // namespace c3
 
 __global__ __launch_bounds__(512) void conv3x3_window_kernel(const float* __restrict__ x,
@@ -483,7 +445,7 @@ __global__ __launch_bounds__(512) void conv3x3_window_kernel(const float* __rest
     cst[1][tid] = alpha ? alpha[tid] : 1.f;
     cst[2][tid] = alpha ? shift[tid] : 0.f;
   }
-  const int HW = H * W, nbx = (W + dcn::TW - 1) / dcn::TW, nby = (H + dcn::WAVES - 1) / dcn::WAVES;
+  const int HW = H * W, nbx = (W + dcn::TW - 1) / dcn::TW, nby = (H + c3::WAVES - 1) / c3::WAVES;
   const int nunits = B * nby * nbx;
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int u_begin = (int)((long long)nunits * bid / gridDim.x);
@@ -492,7 +454,7 @@ __global__ __launch_bounds__(512) void conv3x3_window_kernel(const float* __rest
   floatx4_t stg[c3::STAGE];
   auto fetch = [&](int u) {
     const int b = u / (nby * nbx), rem = u - b * (nby * nbx), band = rem / nbx, xs = rem - band * nbx;
-    const int wy0 = band * dcn::WAVES - c3::HALO, wx0 = xs * dcn::TW - c3::HALO;
+    const int wy0 = band * c3::WAVES - c3::HALO, wx0 = xs * dcn::TW - c3::HALO;
     const __amdgpu_buffer_rsrc_t rx = raw_rsrc(x + (size_t)b * HW * dcn::CI, (unsigned)HW * dcn::CI * 4);
 #pragma unroll
     for (int i = 0; i < c3::STAGE; ++i) {
@@ -514,7 +476,7 @@ __global__ __launch_bounds__(512) void conv3x3_window_kernel(const float* __rest
     }
     __syncthreads();
     if (u + 1 < u_end) fetch(u + 1);
-    const int row = band * dcn::WAVES + wv;
+    const int row = band * c3::WAVES + wv;
     const int x0t = xs * dcn::TW, nvalid = min(dcn::TW, W - x0t);
     if (row >= H) continue;
     floatx4_t acc[2] = {floatx4_t{0.f, 0.f, 0.f, 0.f}, floatx4_t{0.f, 0.f, 0.f, 0.f}};
@@ -650,28 +612,28 @@ extern "C" int tmvs_deform_conv2d_pack(const float* weight, int cout, int cin, f
 
 namespace {
 
-// The DCN unit: kDcnWaves waves (rows) per workgroup with a kDcnHalo-pixel window margin
-constexpr int kDcnWaves = 12, kDcnHalo = 3;
 template <int CO, bool FUSED>
 int dcn_launch(const float* x, const float* om, const float* wom, const float* bom, const float* w,
                const float* bias, const float* alpha, const float* shift, int relu, int batch, int height, int width,
-               float* out, float* out_nhwc, hipStream_t st, float* om_out = nullptr) {
-  constexpr int NW = kDcnWaves, HL = kDcnHalo;
-  // persistent grid: one block per CU slot the kernel's LDS/VGPR footprint allows
-  static int grid = 0;
-  if (!grid) {
-    int dev = 0, ncu = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return TMVS_ERR_HIP;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, dcn_window_kernel<CO, FUSED, NW, HL>, NW * 64, 0);
-    grid = std::max(1, ncu * std::max(occ, 1));
-  }
-  const long long nunits = (long long)batch * ((height + NW - 1) / NW) * ((width + dcn::TW - 1) / dcn::TW);
-  const int nblk = (int)std::min<long long>(grid, nunits);
-  hipLaunchKernelGGL((dcn_window_kernel<CO, FUSED, NW, HL>), dim3(nblk), dim3(NW * 64), 0, st, x, om, wom, bom, w,
-                     bias, alpha, shift, relu, batch, height, width, out, out_nhwc, om_out);
+               float* out, float* out_nhwc, hipStream_t st, float* om_out) {
+  const long long nunits =
+      (long long)batch * ((height + dcn::WAVES - 1) / dcn::WAVES) * ((width + dcn::TW - 1) / dcn::TW);
+  const int nblk = wconv::persistent_blocks<dcn_window_kernel<CO, FUSED>>(dcn::NT, nunits);
+  if (!nblk) return TMVS_ERR_HIP;
+  hipLaunchKernelGGL((dcn_window_kernel<CO, FUSED>), dim3(nblk), dim3(dcn::NT), 0, st, x, om, wom, bom, w, bias, alpha,
+                     shift, relu, batch, height, width, out, out_nhwc, om_out);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
+}
+
+// the DCN instance of cout = 8 / 16 / 32 (dcn_check has admitted no other)
+template <bool FUSED>
+int dcn_dispatch(int cout, const float* x, const float* om, const float* wom, const float* bom, const float* w,
+                 const float* bias, const float* alpha, const float* shift, int relu, int batch, int height, int width,
+                 float* out, float* out_nhwc, void* stream, float* om_out = nullptr) {
+  const auto launch = cout == 32 ? dcn_launch<32, FUSED> : cout == 16 ? dcn_launch<16, FUSED> : dcn_launch<8, FUSED>;
+  return launch(x, om, wom, bom, w, bias, alpha, shift, relu, batch, height, width, out, out_nhwc, (hipStream_t)stream,
+                om_out);
 }
 
 int dcn_check(const float* x_nhwc, const float* w_packed, const float* bias, const float* bn_alpha,
@@ -692,15 +654,8 @@ extern "C" int tmvs_deform_conv2d(const float* x_nhwc, const float* offset_mask,
   if (!offset_mask || !out) return TMVS_ERR_ARG;
   const int rc = dcn_check(x_nhwc, w_packed, bias, bn_alpha, bn_shift, batch, cin, cout, height, width);
   if (rc != TMVS_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (cout == 32)
-    return dcn_launch<32, false>(x_nhwc, offset_mask, nullptr, nullptr, w_packed, bias, bn_alpha, bn_shift, relu,
-                                 batch, height, width, out, out_nhwc, st);
-  if (cout == 16)
-    return dcn_launch<16, false>(x_nhwc, offset_mask, nullptr, nullptr, w_packed, bias, bn_alpha, bn_shift, relu,
-                                 batch, height, width, out, out_nhwc, st);
-  return dcn_launch<8, false>(x_nhwc, offset_mask, nullptr, nullptr, w_packed, bias, bn_alpha, bn_shift, relu, batch,
-                              height, width, out, out_nhwc, st);
+  return dcn_dispatch<false>(cout, x_nhwc, offset_mask, nullptr, nullptr, w_packed, bias, bn_alpha, bn_shift, relu,
+                             batch, height, width, out, out_nhwc, stream);
 }
 
 extern "C" int tmvs_dcn_forward_train(const float* x_nhwc, const float* wom_packed, const float* bom,
@@ -709,15 +664,8 @@ extern "C" int tmvs_dcn_forward_train(const float* x_nhwc, const float* wom_pack
   if (!wom_packed || !bom || !offset_mask_out || (!out && !out_nhwc)) return TMVS_ERR_ARG;
   const int rc = dcn_check(x_nhwc, w_packed, bias, nullptr, nullptr, batch, cin, cout, height, width);
   if (rc != TMVS_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (cout == 32)
-    return dcn_launch<32, true>(x_nhwc, nullptr, wom_packed, bom, w_packed, bias, nullptr, nullptr, 0, batch, height,
-                                width, out, out_nhwc, st, offset_mask_out);
-  if (cout == 16)
-    return dcn_launch<16, true>(x_nhwc, nullptr, wom_packed, bom, w_packed, bias, nullptr, nullptr, 0, batch, height,
-                                width, out, out_nhwc, st, offset_mask_out);
-  return dcn_launch<8, true>(x_nhwc, nullptr, wom_packed, bom, w_packed, bias, nullptr, nullptr, 0, batch, height,
-                             width, out, out_nhwc, st, offset_mask_out);
+  return dcn_dispatch<true>(cout, x_nhwc, nullptr, wom_packed, bom, w_packed, bias, nullptr, nullptr, 0, batch, height,
+                            width, out, out_nhwc, stream, offset_mask_out);
 }
 
 extern "C" int tmvs_dcn_fused(const float* x_nhwc, const float* wom_packed, const float* bom, const float* w_packed,
@@ -726,32 +674,18 @@ extern "C" int tmvs_dcn_fused(const float* x_nhwc, const float* wom_packed, cons
   if (!wom_packed || !bom || (!out && !out_nhwc)) return TMVS_ERR_ARG;
   const int rc = dcn_check(x_nhwc, w_packed, bias, bn_alpha, bn_shift, batch, cin, cout, height, width);
   if (rc != TMVS_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (cout == 32)
-    return dcn_launch<32, true>(x_nhwc, nullptr, wom_packed, bom, w_packed, bias, bn_alpha, bn_shift, relu, batch,
-                                height, width, out, out_nhwc, st);
-  if (cout == 16)
-    return dcn_launch<16, true>(x_nhwc, nullptr, wom_packed, bom, w_packed, bias, bn_alpha, bn_shift, relu, batch,
-                                height, width, out, out_nhwc, st);
-  return dcn_launch<8, true>(x_nhwc, nullptr, wom_packed, bom, w_packed, bias, bn_alpha, bn_shift, relu, batch,
-                             height, width, out, out_nhwc, st);
+  return dcn_dispatch<true>(cout, x_nhwc, nullptr, wom_packed, bom, w_packed, bias, bn_alpha, bn_shift, relu, batch,
+                            height, width, out, out_nhwc, stream);
 }
 
 static int conv3x3_launch(const float* x_nhwc, const float* w_packed, const float* bias, const float* bn_alpha,
                           const float* bn_shift, int flags, int batch, int height, int width, float* out,
                           float* out_nhwc, void* stream) {
   if ((long long)height * width * 32 * 4 >= (1LL << 31)) return TMVS_ERR_SHAPE;
-  static int grid = 0;
-  if (!grid) {
-    int dev = 0, ncu = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return TMVS_ERR_HIP;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv3x3_window_kernel, 512, 0);
-    grid = std::max(1, ncu * std::max(occ, 1));
-  }
   const long long nunits =
-      (long long)batch * ((height + dcn::WAVES - 1) / dcn::WAVES) * ((width + dcn::TW - 1) / dcn::TW);
-  const int nblk = (int)std::min<long long>(grid, nunits);
+      (long long)batch * ((height + c3::WAVES - 1) / c3::WAVES) * ((width + dcn::TW - 1) / dcn::TW);
+  const int nblk = wconv::persistent_blocks<conv3x3_window_kernel>(512, nunits);
+  if (!nblk) return TMVS_ERR_HIP;
   hipLaunchKernelGGL(conv3x3_window_kernel, dim3(nblk), dim3(512), 0, (hipStream_t)stream, x_nhwc, w_packed, bias,
                      bn_alpha, bn_shift, flags, batch, height, width, out, out_nhwc);
   TMVS_CHECK_LAUNCH();

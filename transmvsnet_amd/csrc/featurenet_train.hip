@@ -108,92 +108,12 @@ __global__ __launch_bounds__(kBlk) void conv2d_generic_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------- pixel-reduction helpers
-// A register-tiled reduction sum_p a[p][i] * b[p][j] over a block's pixel range [v0, v1): chunks of
-// 64 rows are staged in LDS by the callers' row loaders (float4 quads, zero rows where the gathered
-// tap is outside); lane (ai, ci) of each wave owns a TA x TB block, fp32 per chunk, fp64 across
-// chunks; the 4 waves combine in the fixed order ((w0 + w1) + w2) + w3. A = rows of `a` (padded to
-// a multiple of 8 by the loader), BC = columns of `b` (multiple of 8).
-template <int A, int BC, typename LoadA, typename LoadB>
-__device__ __forceinline__ void tile_reduce(long v0, long v1, LoadA load_a, LoadB load_b, double* __restrict__ out) {
-  constexpr int CH = 64, TA = A / 8, TB = BC / 8, SA = A + 4, SB = BC + 4;
-  static_assert(A % 8 == 0 && BC % 8 == 0, "tile");
-  static_assert(CH * (SA + SB) * 4 >= A * BC * 8, "combine buffer fits the staging LDS");
-  __shared__ __attribute__((aligned(16))) float lds[CH * (SA + SB)];
-  float* sa = lds;
-  float* sb = lds + CH * SA;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int ci = lane & 7, ai = lane >> 3;
-  double acc[TA][TB];
-#pragma unroll
-  for (int i = 0; i < TA; ++i)
-#pragma unroll
-    for (int j = 0; j < TB; ++j) acc[i][j] = 0.0;
-#pragma unroll 1
-  for (long vb = v0; vb < v1; vb += CH) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < CH * A / 4; i += kBlk) {
-      const int r = i / (A / 4), q = i % (A / 4);
-      const long v = vb + r;
-      *reinterpret_cast<float4*>(sa + r * SA + 4 * q) = v < v1 ? load_a(v, q) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    for (int i = threadIdx.x; i < CH * BC / 4; i += kBlk) {
-      const int r = i / (BC / 4), q = i % (BC / 4);
-      const long v = vb + r;
-      *reinterpret_cast<float4*>(sb + r * SB + 4 * q) = v < v1 ? load_b(v, q) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();
-    float s[TA][TB];
-#pragma unroll
-    for (int i = 0; i < TA; ++i)
-#pragma unroll
-      for (int j = 0; j < TB; ++j) s[i][j] = 0.f;
-#pragma unroll 4
-    for (int r = wv; r < CH; r += 4) {
-      float av[TA], bv[TB];
-#pragma unroll
-      for (int i = 0; i < TA; ++i) av[i] = sa[r * SA + ai * TA + i];
-#pragma unroll
-      for (int j = 0; j < TB; ++j) bv[j] = sb[r * SB + ci * TB + j];
-#pragma unroll
-      for (int i = 0; i < TA; ++i)
-#pragma unroll
-        for (int j = 0; j < TB; ++j) s[i][j] = fmaf(av[i], bv[j], s[i][j]);
-    }
-#pragma unroll
-    for (int i = 0; i < TA; ++i)
-#pragma unroll
-      for (int j = 0; j < TB; ++j) acc[i][j] += (double)s[i][j];
-  }
-  double* cmb = reinterpret_cast<double*>(lds);
-#pragma unroll 1
-  for (int w = 1; w < 4; ++w) {
-    __syncthreads();
-    if (wv == w)
-#pragma unroll
-      for (int i = 0; i < TA; ++i)
-#pragma unroll
-        for (int j = 0; j < TB; ++j) cmb[(ai * TA + i) * BC + ci * TB + j] = acc[i][j];
-    __syncthreads();
-    if (wv == 0)
-#pragma unroll
-      for (int i = 0; i < TA; ++i)
-#pragma unroll
-        for (int j = 0; j < TB; ++j) acc[i][j] += cmb[(ai * TA + i) * BC + ci * TB + j];
-  }
-  if (wv == 0)
-#pragma unroll
-    for (int i = 0; i < TA; ++i)
-#pragma unroll
-      for (int j = 0; j < TB; ++j) out[(ai * TA + i) * BC + ci * TB + j] = acc[i][j];
-}
-
-// the matrix-core form (reduce_mfma.h) wherever both sides have >= 8 channels
+// The reduction sum_p a[p][i] * b[p][j] over a block's pixel range [v0, v1): tile_reduce_mfma (reduce_mfma.h).
+// A = rows of `a` (padded to a multiple of 8 by the loader), BC = columns of `b` (a multiple of 8).
 template <int A, int BC, bool BROW = false, typename LoadA, typename LoadB>
-__device__ __forceinline__ void tile_reduce_any(long v0, long v1, LoadA load_a, LoadB load_b, double* __restrict__ out) {
-  if constexpr (A % 8 == 0 && BC % 8 == 0)
-    tile_reduce_mfma<A, BC, BROW>(v0, v1, load_a, load_b, out);
-  else
-    tile_reduce<A, BC>(v0, v1, load_a, load_b, out);
+__device__ __forceinline__ void tile_reduce(long v0, long v1, LoadA load_a, LoadB load_b, double* __restrict__ out) {
+  static_assert(A % 8 == 0 && BC % 8 == 0, "the matrix-core reduction's tile");
+  tile_reduce_mfma<A, BC, BROW>(v0, v1, load_a, load_b, out);
 }
 
 __device__ __forceinline__ float4 load_row4(const float* __restrict__ base, long v, int ch, int q) {
@@ -224,7 +144,7 @@ __global__ __launch_bounds__(kBlk) void conv2d_wgrad_kernel(const float* __restr
     if (gh < 0 || gw < 0 || gh >= Gh || gw >= Gw) return make_float4(0.f, 0.f, 0.f, 0.f);
     return *reinterpret_cast<const float4*>(gath + (((size_t)b * Gh + gh) * Gw + gw) * BC + 4 * q);
   };
-  tile_reduce_any<AP, BC>(v0, v1, la, lb, partial + ((size_t)rb * K * K + k) * AP * BC);
+  tile_reduce<AP, BC>(v0, v1, la, lb, partial + ((size_t)rb * K * K + k) * AP * BC);
 }
 
 // few channels on the gathered side (the image: 3): thread t owns pairs t, t+256, .. of a x b,
@@ -668,7 +588,7 @@ __global__ __launch_bounds__(kBlk) void dcn_bwd_weight_kernel(const float* __res
     o[0] = col_quad(s, b, q0);
     o[1] = col_quad(s, b, q0 + 1);
   };
-  tile_reduce_any<CO, 32, true>(v0, v1, la, lb, partial + ((size_t)rb * 9 + k) * CO * 32);
+  tile_reduce<CO, 32, true>(v0, v1, la, lb, partial + ((size_t)rb * 9 + k) * CO * 32);
 }
 
 // ---------------------------------------------------------------- small backward pieces
