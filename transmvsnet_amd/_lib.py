@@ -127,6 +127,22 @@ SIGNATURES = {
     "tmvs_dtu_above_plane": (I, [P, L, P, P, P]),
 }
 
+# name -> (restype, argtypes); every symbol include/transmvs_sync.h declares (BatchNorm statistics synchronised
+# across ranks: sync_bn.py)
+SYNC_SIGNATURES = {
+    "tmvs_rank_sum": (I, [P, I, L, P, P]),
+    "tmvs_bn_moments_grouped": (I, [P, I, L, I, P, S, P, P]),
+    "tmvs_bn_stats_from_sums": (I, [P, I, I, L, P, P, P]),
+    "tmvs_bn_relu_backward_sums_grouped": (I, [P, P, I, L, I, P, P, P, P, F, P, S, P, P, P, P]),
+    "tmvs_bn_relu_backward_apply_grouped": (I, [P, P, I, L, I, P, P, P, P, F, P, L, P, P]),
+    "tmvs_pw_sync_forward_sums": (I, [P, I, I, I, I, I, P, S, P, P]),
+    "tmvs_pw_sync_forward_z1": (I, [P, I, I, I, I, I, P, P, L, P, S, P, P, P]),
+    "tmvs_pw_sync_forward_weights": (I, [P, I, I, I, I, I, P, P, L, P, P, P, P]),
+    "tmvs_pw_sync_backward_s1": (I, [P, I, I, I, I, I, P, P, P, P, P, P, S, P, P]),
+    "tmvs_pw_sync_backward_s2": (I, [P, I, I, I, I, I, P, P, P, P, P, P, L, P, S, P, P]),
+    "tmvs_pw_sync_backward_apply": (I, [P, I, I, I, I, I, P, P, P, P, P, P, P, L, P, P, P, S, P, P, P]),
+}
+
 ABI_VERSION = 11
 PW_NPARAMS = 201
 ENC_NPARAMS = 8544
@@ -161,7 +177,7 @@ def load():
         raise RuntimeError(f"transmvsnet_amd HIP extension not built ({LIB_PATH} missing): "
                            "run `python -m transmvsnet_amd.build`")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in (*SIGNATURES.items(), *SYNC_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -23,6 +23,7 @@
 // Bounds: the convolutions are fp32 FMA work (VALU; 3 x 3,456 MAC per voxel for forward + both
 // gradients), the BN passes HBM (2-3 reads of z per pass).
 #include "train_reduce.h"
+#include "../../include/transmvs_sync.h"
 
 namespace tmvs {
 
@@ -434,7 +435,7 @@ __global__ __launch_bounds__(kTrainBlock) void bn_relu_bwd_partial_kernel(
 __device__ __forceinline__ void bn_relu_bwd_finalize(const double* __restrict__ sums, int C, int groups,
                                                      float* __restrict__ dgamma, float* __restrict__ dbeta) {
   const int c = threadIdx.x;
-  if (blockIdx.x != 0 || c >= C) return;
+  if (!dgamma || blockIdx.x != 0 || c >= C) return;  // (no dgamma: the split entries finalize on their own sums)
   float b = (float)sums[c], g = (float)sums[C + c];
   for (int k = 1; k < groups; ++k) {
     b = b + (float)sums[(size_t)k * 2 * C + c];
@@ -445,13 +446,14 @@ __device__ __forceinline__ void bn_relu_bwd_finalize(const double* __restrict__ 
 }
 
 // pass 2: dz = gamma*rstd/N * (N*g - sum g - xhat * sum g*xhat); VEC elements per thread as
-// bn_relu_apply_kernel (one body per element, the same bits)
+// bn_relu_apply_kernel (one body per element, the same bits). N = n_total, the count behind `sums`: the
+// group's nvox, or with statistics synchronised across ranks the count of all ranks' elements
 template <int VEC>
 __global__ __launch_bounds__(kTrainBlock) void bn_relu_bwd_apply_kernel(
-    const float* __restrict__ dy, const float* __restrict__ z, long nv, int C, long nvox, const float* __restrict__ mean,
-    const float* __restrict__ var, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-    const double* __restrict__ sums, int groups, float* __restrict__ dgamma, float* __restrict__ dbeta,
-    float* __restrict__ dz) {
+    const float* __restrict__ dy, const float* __restrict__ z, long nv, int C, long nvox, long n_total,
+    const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float eps, const double* __restrict__ sums, int groups,
+    float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dz) {
   bn_relu_bwd_finalize(sums, C, groups, dgamma, dbeta);
   const long iv = (long)blockIdx.x * kTrainBlock + threadIdx.x;
   if (iv >= nv) return;
@@ -463,7 +465,7 @@ __global__ __launch_bounds__(kTrainBlock) void bn_relu_bwd_apply_kernel(
   float zz[VEC], dd[VEC], o[VEC];
   load_vec<VEC>(z + i, zz);
   load_vec<VEC>(dy + i, dd);
-  const double inv_n = 1.0 / (double)nvox;
+  const double inv_n = 1.0 / (double)n_total;
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
     const int c = c0 + j;
@@ -636,6 +638,38 @@ extern "C" int tmvs_bn_relu_train(const float* z, long nvox, int channels, const
   return tmvs_bn_relu_train_grouped(z, 1, nvox, channels, mean, var, gamma, beta, eps, skip, out, stream);
 }
 
+// the backward's two halves, the sums and the apply: tmvs_bn_relu_backward_grouped runs one after the other, the
+// split entries (include/transmvs_sync.h) one each, with the sums of all ranks in between
+static int bn_launch_bwd_sums(const float* dy, const float* z, int groups, long nvox, int channels, const float* mean,
+                              const float* var, const float* gamma, const float* beta, float eps, double* part,
+                              double* sums, hipStream_t st) {
+  const auto [vpb, nblk] = bn_chunk(nvox);
+  hipLaunchKernelGGL(bn_relu_bwd_partial_kernel, dim3(nblk, groups), dim3(kTrainBlock), 0, st, dy, z, nvox, channels,
+                     mean, var, gamma, beta, eps, vpb, part);
+  TMVS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(2 * channels, groups), dim3(kTrainBlock), 0, st,
+                     (const double*)part, nblk, 2 * channels, sums);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
+static int bn_launch_bwd_apply(const float* dy, const float* z, int groups, long nvox, int channels, long n_total,
+                               const float* mean, const float* var, const float* gamma, const float* beta, float eps,
+                               const double* sums, float* dz, float* dgamma, float* dbeta, hipStream_t st) {
+  const long n = nvox * channels * groups;
+  if (channels % 4 == 0 && aligned16(dy) && aligned16(z) && aligned16(dz)) {
+    hipLaunchKernelGGL(bn_relu_bwd_apply_kernel<4>, dim3((unsigned)((n / 4 + kTrainBlock - 1) / kTrainBlock)),
+                       dim3(kTrainBlock), 0, st, dy, z, n / 4, channels, nvox, n_total, mean, var, gamma, beta, eps,
+                       sums, groups, dgamma, dbeta, dz);
+  } else {
+    hipLaunchKernelGGL(bn_relu_bwd_apply_kernel<1>, dim3((unsigned)((n + kTrainBlock - 1) / kTrainBlock)),
+                       dim3(kTrainBlock), 0, st, dy, z, n, channels, nvox, n_total, mean, var, gamma, beta, eps, sums,
+                       groups, dgamma, dbeta, dz);
+  }
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
 extern "C" int tmvs_bn_relu_backward_grouped(const float* dy, const float* z, int groups, long nvox, int channels,
                                              const float* mean, const float* var, const float* gamma,
                                              const float* beta, float eps, void* workspace, size_t workspace_bytes,
@@ -646,27 +680,11 @@ extern "C" int tmvs_bn_relu_backward_grouped(const float* dy, const float* z, in
   if (channels <= 0 || kTrainBlock % channels) return TMVS_ERR_SHAPE;
   if (workspace_bytes < tmvs_bn_train_workspace_grouped(groups, nvox, channels)) return TMVS_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const auto [vpb, nblk] = bn_chunk(nvox);
   double* part = (double*)workspace;
-  double* sums = part + (size_t)groups * nblk * 2 * channels;
-  hipLaunchKernelGGL(bn_relu_bwd_partial_kernel, dim3(nblk, groups), dim3(kTrainBlock), 0, st, dy, z, nvox, channels,
-                     mean, var, gamma, beta, eps, vpb, part);
-  TMVS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(2 * channels, groups), dim3(kTrainBlock), 0, st,
-                     (const double*)part, nblk, 2 * channels, sums);
-  TMVS_CHECK_LAUNCH();
-  const long n = nvox * channels * groups;
-  if (channels % 4 == 0 && aligned16(dy) && aligned16(z) && aligned16(dz)) {
-    hipLaunchKernelGGL(bn_relu_bwd_apply_kernel<4>, dim3((unsigned)((n / 4 + kTrainBlock - 1) / kTrainBlock)),
-                       dim3(kTrainBlock), 0, st, dy, z, n / 4, channels, nvox, mean, var, gamma, beta, eps,
-                       (const double*)sums, groups, dgamma, dbeta, dz);
-  } else {
-    hipLaunchKernelGGL(bn_relu_bwd_apply_kernel<1>, dim3((unsigned)((n + kTrainBlock - 1) / kTrainBlock)),
-                       dim3(kTrainBlock), 0, st, dy, z, n, channels, nvox, mean, var, gamma, beta, eps,
-                       (const double*)sums, groups, dgamma, dbeta, dz);
-  }
-  TMVS_CHECK_LAUNCH();
-  return TMVS_OK;
+  double* sums = part + (size_t)groups * bn_chunk(nvox).blocks * 2 * channels;
+  if (int e = bn_launch_bwd_sums(dy, z, groups, nvox, channels, mean, var, gamma, beta, eps, part, sums, st)) return e;
+  return bn_launch_bwd_apply(dy, z, groups, nvox, channels, nvox, mean, var, gamma, beta, eps, sums, dz, dgamma, dbeta,
+                             st);
 }
 
 extern "C" int tmvs_bn_relu_backward(const float* dy, const float* z, long nvox, int channels, const float* mean,
@@ -675,4 +693,82 @@ extern "C" int tmvs_bn_relu_backward(const float* dy, const float* z, long nvox,
                                      void* stream) {
   return tmvs_bn_relu_backward_grouped(dy, z, 1, nvox, channels, mean, var, gamma, beta, eps, workspace,
                                        workspace_bytes, dz, dgamma, dbeta, stream);
+}
+
+// ---------------------------------------------------------------- statistics synchronised across ranks
+// (include/transmvs_sync.h) The same passes, cut where the sums cross ranks: the fp64 [groups][2][C] sums come
+// out before any finalize and go back in as the sums of all ranks with their count n_total. With the local sums
+// and n_total = nvox every output is bitwise the fused entries'.
+__global__ void bn_stats_from_sums_kernel(const double* __restrict__ sums, int n, int C, long n_total,
+                                          float* __restrict__ mean, float* __restrict__ var) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // (group, channel)
+  if (i >= n) return;
+  const int g = i / C, c = i - g * C;
+  bn_stats_from_sums(sums[(size_t)g * 2 * C + c], sums[(size_t)g * 2 * C + C + c], n_total, mean[i], var[i]);
+}
+
+__global__ __launch_bounds__(kTrainBlock) void bn_relu_bwd_finalize_kernel(const double* __restrict__ sums, int C,
+                                                                           int groups, float* __restrict__ dgamma,
+                                                                           float* __restrict__ dbeta) {
+  bn_relu_bwd_finalize(sums, C, groups, dgamma, dbeta);
+}
+
+extern "C" int tmvs_bn_moments_grouped(const float* z, int groups, long nvox, int channels, void* workspace,
+                                       size_t workspace_bytes, double* sums, void* stream) {
+  if (!z || !workspace || !sums || nvox <= 0 || groups <= 0) return TMVS_ERR_ARG;
+  if (channels <= 0 || kTrainBlock % channels) return TMVS_ERR_SHAPE;
+  if (workspace_bytes < tmvs_bn_train_workspace_grouped(groups, nvox, channels)) return TMVS_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const auto [vpb, nblk] = bn_chunk(nvox);
+  double* part = (double*)workspace;
+  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nblk, groups), dim3(kTrainBlock), 0, st, z, nvox, channels, vpb,
+                     part);
+  TMVS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(2 * channels, groups), dim3(kTrainBlock), 0, st,
+                     (const double*)part, nblk, 2 * channels, sums);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
+extern "C" int tmvs_bn_stats_from_sums(const double* sums, int groups, int channels, long n_total, float* mean,
+                                       float* var, void* stream) {
+  if (!sums || !mean || !var || groups <= 0 || n_total <= 0) return TMVS_ERR_ARG;
+  if (channels <= 0 || kTrainBlock % channels) return TMVS_ERR_SHAPE;
+  const int n = groups * channels;
+  hipLaunchKernelGGL(bn_stats_from_sums_kernel, dim3((n + kTrainBlock - 1) / kTrainBlock), dim3(kTrainBlock), 0,
+                     (hipStream_t)stream, sums, n, channels, n_total, mean, var);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
+extern "C" int tmvs_bn_relu_backward_sums_grouped(const float* dy, const float* z, int groups, long nvox, int channels,
+                                                  const float* mean, const float* var, const float* gamma,
+                                                  const float* beta, float eps, void* workspace,
+                                                  size_t workspace_bytes, double* sums, float* dgamma, float* dbeta,
+                                                  void* stream) {
+  if (!dy || !z || !mean || !var || !gamma || !beta || !workspace || !sums || !dgamma || !dbeta || nvox <= 0 ||
+      groups <= 0)
+    return TMVS_ERR_ARG;
+  if (channels <= 0 || kTrainBlock % channels) return TMVS_ERR_SHAPE;
+  if (workspace_bytes < tmvs_bn_train_workspace_grouped(groups, nvox, channels)) return TMVS_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (int e = bn_launch_bwd_sums(dy, z, groups, nvox, channels, mean, var, gamma, beta, eps, (double*)workspace, sums,
+                                 st))
+    return e;
+  hipLaunchKernelGGL(bn_relu_bwd_finalize_kernel, dim3(1), dim3(kTrainBlock), 0, st, (const double*)sums, channels,
+                     groups, dgamma, dbeta);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
+extern "C" int tmvs_bn_relu_backward_apply_grouped(const float* dy, const float* z, int groups, long nvox,
+                                                   int channels, const float* mean, const float* var,
+                                                   const float* gamma, const float* beta, float eps,
+                                                   const double* global_sums, long n_total, float* dz, void* stream) {
+  if (!dy || !z || !mean || !var || !gamma || !beta || !global_sums || !dz || nvox <= 0 || groups <= 0 ||
+      n_total < nvox)
+    return TMVS_ERR_ARG;
+  if (channels <= 0 || kTrainBlock % channels) return TMVS_ERR_SHAPE;
+  return bn_launch_bwd_apply(dy, z, groups, nvox, channels, n_total, mean, var, gamma, beta, eps, global_sums, dz,
+                             nullptr, nullptr, (hipStream_t)stream);
 }

@@ -13,6 +13,7 @@
 // Every reduction is fp64 block partials + a fixed-order combine (deterministic, no atomics);
 // the backward recomputes the forward chain per element instead of storing 24 channels per voxel.
 #include "train_reduce.h"
+#include "../../include/transmvs_sync.h"
 
 namespace tmvs {
 
@@ -282,9 +283,10 @@ __global__ __launch_bounds__(kPwBlock) void pw_bwd2_kernel(const float* __restri
                                                            const float* __restrict__ w, const int* __restrict__ dstar,
                                                            const float* __restrict__ dw, const double* __restrict__ s1,
                                                            int B, long bstride, long wstride, long epb,
-                                                           double* __restrict__ partial) {
+                                                           long n_total, double* __restrict__ partial) {
   const long n = (long)D * P, tot = (long)B * n;
-  const double inv_n = 1.0 / (double)tot;  // the BatchNorm's count: the view's whole batch
+  // the BatchNorm's count behind s1: the view's whole batch (tot), on all ranks when they share statistics
+  const double inv_n = 1.0 / (double)n_total;
   float acc[160];  // g0 sums [0,16), g0*xhat0 sums [16,32), dW1 [32,160)
 #pragma unroll
   for (int i = 0; i < 160; ++i) acc[i] = 0.f;
@@ -323,10 +325,10 @@ __global__ __launch_bounds__(kPwBlock) void pw_bwd3_kernel(const float* __restri
                                                            const float* __restrict__ w, const int* __restrict__ dstar,
                                                            const float* __restrict__ dw, const double* __restrict__ s1,
                                                            const double* __restrict__ s2, int B, long bstride,
-                                                           long wstride, long epb,
+                                                           long wstride, long epb, long n_total,
                                                            float* __restrict__ dsims, double* __restrict__ partial) {
   const long n = (long)D * P, tot = (long)B * n;
-  const double inv_n = 1.0 / (double)tot;
+  const double inv_n = 1.0 / (double)n_total;
   double v[16];
 #pragma unroll
   for (int j = 0; j < 16; ++j) v[j] = 0.0;
@@ -400,33 +402,64 @@ static bool pw_batch_fits(int batch, int n_views, int ndepth, int height, int wi
   return batch * P < (1L << 31) - kPwBlock && (double)batch * n_views * ndepth * (double)P < 9e18;
 }
 
+// One call's geometry and the launch of each stage of a view's passes. The fused entries run a view's stages
+// back to back on sums in the workspace; the staged ones (include/transmvs_sync.h) run one stage over all
+// views, so that the fp64 sums between two stages can be added over ranks. Same kernels, same arguments.
+struct PwGeo {
+  int B, V, D, P;
+  long n, tot, bstride, wstride;
+  Chunk ce, cp;  // element and pixel ranges of the partial passes
+  PwGeo(int batch, int n_views, int ndepth, int height, int width)
+      : B(batch), V(n_views), D(ndepth), P(height * width), n((long)ndepth * P), tot((long)batch * n),
+        bstride((long)n_views * n), wstride((long)n_views * P), ce(pw_chunk(tot)), cp(pw_chunk((long)batch * P)) {}
+};
+
+static bool pw_dims_ok(int batch, int n_views, int ndepth, int height, int width) {
+  return batch > 0 && n_views > 0 && ndepth > 0 && height > 0 && width > 0;
+}
+
+// stage 1: sums[2] = (sum s, sum s^2) of view v
+static void pw_fwd_s_sums(const PwGeo& g, const float* sims, int v, double* part, double* sums, hipStream_t st) {
+  hipLaunchKernelGGL(pw_s_partial_kernel, dim3(g.ce.blocks), dim3(kPwBlock), 0, st, sims + (size_t)v * g.n, g.n, g.tot,
+                     g.bstride, g.ce.rows, part);
+  hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(2), dim3(kPwBlock), 0, st, (const double*)part, g.ce.blocks, 2,
+                     sums);
+}
+
+// stage 2: layer-0 statistics from the sums over n_total elements, then sums[16] = (sum z1, sum z1^2)
+static void pw_fwd_z1_sums(const PwGeo& g, const float* sims, int v, const float* pwp, const double* s_sums,
+                           long n_total, float* sv, double* part, double* sums, hipStream_t st) {
+  hipLaunchKernelGGL(pw_stats0_kernel, dim3(1), dim3(64), 0, st, s_sums, n_total, pwp, sv);
+  hipLaunchKernelGGL(pw_z1_partial_kernel, dim3(g.ce.blocks), dim3(kPwBlock), 0, st, sims + (size_t)v * g.n, g.n, g.tot,
+                     g.bstride, g.ce.rows, pwp, (const float*)sv, part);
+  hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(16), dim3(kPwBlock), 0, st, (const double*)part, g.ce.blocks, 16,
+                     sums);
+}
+
+// stage 3: layer-1 statistics, then the view's weights and argmax
+static void pw_fwd_weights(const PwGeo& g, const float* sims, int v, const float* pwp, const double* z1_sums,
+                           long n_total, float* sv, float* view_w, int* dstar, hipStream_t st) {
+  hipLaunchKernelGGL(pw_stats1_kernel, dim3(1), dim3(64), 0, st, z1_sums, n_total, sv);
+  hipLaunchKernelGGL(pw_weight_kernel, dim3((g.B * g.P + kPwBlock - 1) / kPwBlock), dim3(kPwBlock), 0, st,
+                     sims + (size_t)v * g.n, g.B, g.D, g.P, g.bstride, g.wstride, pwp, (const float*)sv,
+                     view_w + (size_t)v * g.P, dstar + (size_t)v * g.P);
+}
+
 static int pw_forward(const float* sims, int batch, int n_views, int ndepth, int height, int width, const float* pwp,
                       void* workspace, size_t workspace_bytes, float* stats, float* view_w, int* dstar, void* stream) {
-  if (!sims || !pwp || !workspace || !stats || !view_w || !dstar || batch <= 0 || n_views <= 0 || ndepth <= 0 ||
-      height <= 0 || width <= 0)
+  if (!sims || !pwp || !workspace || !stats || !view_w || !dstar || !pw_dims_ok(batch, n_views, ndepth, height, width))
     return TMVS_ERR_ARG;
   if (workspace_bytes < tmvs_pixelwise_train_workspace()) return TMVS_ERR_ARG;
   if (!pw_batch_fits(batch, n_views, ndepth, height, width)) return TMVS_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const int P = height * width;
-  const long n = (long)ndepth * P, tot = (long)batch * n;
-  const long bstride = (long)n_views * n, wstride = (long)n_views * P;  // sample to sample
+  const PwGeo g(batch, n_views, ndepth, height, width);
   double* part = (double*)workspace;
   double* sums = part + 1024 * 160;
-  const auto [c, nb] = pw_chunk(tot);
   for (int v = 0; v < n_views; ++v) {
-    const float* s = sims + (size_t)v * n;
     float* sv = stats + (size_t)v * 48;
-    hipLaunchKernelGGL(pw_s_partial_kernel, dim3(nb), dim3(kPwBlock), 0, st, s, n, tot, bstride, c, part);
-    hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(2), dim3(kPwBlock), 0, st, (const double*)part, nb, 2, sums);
-    hipLaunchKernelGGL(pw_stats0_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, tot, pwp, sv);
-    hipLaunchKernelGGL(pw_z1_partial_kernel, dim3(nb), dim3(kPwBlock), 0, st, s, n, tot, bstride, c, pwp,
-                       (const float*)sv, part);
-    hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(16), dim3(kPwBlock), 0, st, (const double*)part, nb, 16, sums);
-    hipLaunchKernelGGL(pw_stats1_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, tot, sv);
-    hipLaunchKernelGGL(pw_weight_kernel, dim3((batch * P + kPwBlock - 1) / kPwBlock), dim3(kPwBlock), 0, st, s, batch,
-                       ndepth, P, bstride, wstride, pwp, (const float*)sv, view_w + (size_t)v * P,
-                       dstar + (size_t)v * P);
+    pw_fwd_s_sums(g, sims, v, part, sums, st);
+    pw_fwd_z1_sums(g, sims, v, pwp, sums, g.tot, sv, part, sums, st);
+    pw_fwd_weights(g, sims, v, pwp, sums, g.tot, sv, view_w, dstar, st);
     TMVS_CHECK_LAUNCH();
   }
   return TMVS_OK;
@@ -474,39 +507,60 @@ extern "C" int tmvs_aggregate_train_backward(const float* dsim, const float* sim
   return TMVS_OK;
 }
 
+struct PwSaved {  // what the backward reads of the forward, per call
+  const float *sims, *pwp, *stats, *view_w, *dview_w;
+  const int* dstar;
+};
+
+// backward stage 1: s1[25] of view v
+static void pw_bwd_s1(const PwGeo& g, const PwSaved& f, int v, double* part, double* s1, hipStream_t st) {
+  hipLaunchKernelGGL(pw_bwd1_kernel, dim3(g.cp.blocks), dim3(kPwBlock), 0, st, f.sims + (size_t)v * g.n, g.D, g.P,
+                     f.pwp, f.stats + (size_t)v * 48, f.view_w + (size_t)v * g.P, f.dstar + (size_t)v * g.P,
+                     f.dview_w + (size_t)v * g.P, g.B, g.bstride, g.wstride, g.cp.rows, part);
+  hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(25), dim3(kPwBlock), 0, st, (const double*)part, g.cp.blocks, 25,
+                     s1);
+}
+
+// backward stage 2: s2[160] of view v from the BatchNorm sums of s1 over n_total elements
+static void pw_bwd_s2(const PwGeo& g, const PwSaved& f, int v, const double* s1, long n_total, double* part,
+                      double* s2, hipStream_t st) {
+  hipLaunchKernelGGL(pw_bwd2_kernel, dim3(g.ce.blocks), dim3(kPwBlock), 0, st, f.sims + (size_t)v * g.n, g.D, g.P,
+                     f.pwp, f.stats + (size_t)v * 48, f.view_w + (size_t)v * g.P, f.dstar + (size_t)v * g.P,
+                     f.dview_w + (size_t)v * g.P, s1, g.B, g.bstride, g.wstride, g.ce.rows, n_total, part);
+  hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(160), dim3(kPwBlock), 0, st, (const double*)part, g.ce.blocks,
+                     160, s2);
+}
+
+// backward stage 3: dsims and s3[16] of view v from the BatchNorm sums of s1 and s2 over n_total elements
+static void pw_bwd_s3(const PwGeo& g, const PwSaved& f, int v, const double* s1, const double* s2, long n_total,
+                      float* dsims, double* part, double* s3, hipStream_t st) {
+  hipLaunchKernelGGL(pw_bwd3_kernel, dim3(g.ce.blocks), dim3(kPwBlock), 0, st, f.sims + (size_t)v * g.n, g.D, g.P,
+                     f.pwp, f.stats + (size_t)v * 48, f.view_w + (size_t)v * g.P, f.dstar + (size_t)v * g.P,
+                     f.dview_w + (size_t)v * g.P, s1, s2, g.B, g.bstride, g.wstride, g.ce.rows, n_total,
+                     dsims + (size_t)v * g.n, part);
+  hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(16), dim3(kPwBlock), 0, st, (const double*)part, g.ce.blocks, 16,
+                     s3);
+}
+
 static int pw_backward(const float* sims, int batch, int n_views, int ndepth, int height, int width, const float* pwp,
                        const float* stats, const float* view_w, const int* dstar, const float* dview_w,
                        void* workspace, size_t workspace_bytes, float* dsims, float* dpwp, void* stream) {
-  if (!sims || !pwp || !stats || !view_w || !dstar || !dview_w || !workspace || !dsims || !dpwp || batch <= 0 ||
-      n_views <= 0 || ndepth <= 0 || height <= 0 || width <= 0)
+  if (!sims || !pwp || !stats || !view_w || !dstar || !dview_w || !workspace || !dsims || !dpwp ||
+      !pw_dims_ok(batch, n_views, ndepth, height, width))
     return TMVS_ERR_ARG;
   if (workspace_bytes < tmvs_pixelwise_train_workspace()) return TMVS_ERR_ARG;
   if (!pw_batch_fits(batch, n_views, ndepth, height, width)) return TMVS_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const int P = height * width;
-  const long n = (long)ndepth * P;
-  const long bstride = (long)n_views * n, wstride = (long)n_views * P;
+  const PwGeo g(batch, n_views, ndepth, height, width);
+  const PwSaved f{sims, pwp, stats, view_w, dview_w, dstar};
   double* part = (double*)workspace;
   double* s1 = part + 1024 * 160;
   double* s2 = s1 + 32;
   double* s3 = s2 + 160;
-  const auto [cp, nbp] = pw_chunk((long)batch * P);
-  const auto [ce, nbe] = pw_chunk((long)batch * n);
   for (int v = 0; v < n_views; ++v) {
-    const float* s = sims + (size_t)v * n;
-    const float* sv = stats + (size_t)v * 48;
-    const float* w = view_w + (size_t)v * P;
-    const int* ds = dstar + (size_t)v * P;
-    const float* dw = dview_w + (size_t)v * P;
-    hipLaunchKernelGGL(pw_bwd1_kernel, dim3(nbp), dim3(kPwBlock), 0, st, s, ndepth, P, pwp, sv, w, ds, dw, batch,
-                       bstride, wstride, cp, part);
-    hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(25), dim3(kPwBlock), 0, st, (const double*)part, nbp, 25, s1);
-    hipLaunchKernelGGL(pw_bwd2_kernel, dim3(nbe), dim3(kPwBlock), 0, st, s, ndepth, P, pwp, sv, w, ds, dw,
-                       (const double*)s1, batch, bstride, wstride, ce, part);
-    hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(160), dim3(kPwBlock), 0, st, (const double*)part, nbe, 160, s2);
-    hipLaunchKernelGGL(pw_bwd3_kernel, dim3(nbe), dim3(kPwBlock), 0, st, s, ndepth, P, pwp, sv, w, ds, dw,
-                       (const double*)s1, (const double*)s2, batch, bstride, wstride, ce, dsims + (size_t)v * n, part);
-    hipLaunchKernelGGL(sum_partials_f64_kernel<>, dim3(16), dim3(kPwBlock), 0, st, (const double*)part, nbe, 16, s3);
+    pw_bwd_s1(g, f, v, part, s1, st);
+    pw_bwd_s2(g, f, v, s1, g.tot, part, s2, st);
+    pw_bwd_s3(g, f, v, s1, s2, g.tot, dsims, part, s3, st);
     hipLaunchKernelGGL(pw_grad_finalize_kernel, dim3(1), dim3(128), 0, st, (const double*)s1, (const double*)s2,
                        (const double*)s3, dpwp);
     TMVS_CHECK_LAUNCH();
@@ -529,4 +583,105 @@ extern "C" int tmvs_pixelwise_train_backward_batched(const float* sims, int batc
                                                      float* dpwp, void* stream) {
   return pw_backward(sims, batch, n_views, ndepth, height, width, pwp, stats, view_w, dstar, dview_w, workspace,
                      workspace_bytes, dsims, dpwp, stream);
+}
+
+// ---------------------------------------------------------------- statistics synchronised across ranks
+// (include/transmvs_sync.h) The passes above stage-major over the views: each entry runs one stage for all V
+// views and returns (or takes) that stage's fp64 sums [V][K], so one collective per stage serves every view.
+// Fed the local sums and n_total = B*D*P, the six entries are tmvs_pixelwise_train_*_batched bit for bit.
+static int pw_sync_check(const void* const* ptrs, int nptrs, int batch, int n_views, int ndepth, int height, int width,
+                         long n_total, bool has_ws, size_t workspace_bytes) {
+  for (int i = 0; i < nptrs; ++i)
+    if (!ptrs[i]) return TMVS_ERR_ARG;
+  if (!pw_dims_ok(batch, n_views, ndepth, height, width)) return TMVS_ERR_ARG;
+  if (has_ws && workspace_bytes < tmvs_pixelwise_train_workspace()) return TMVS_ERR_ARG;
+  if (!pw_batch_fits(batch, n_views, ndepth, height, width)) return TMVS_ERR_SHAPE;
+  if (n_total < (long)batch * ndepth * height * width) return TMVS_ERR_ARG;  // fewer elements than this rank's own
+  return TMVS_OK;
+}
+
+extern "C" int tmvs_pw_sync_forward_sums(const float* sims, int batch, int n_views, int ndepth, int height, int width,
+                                         void* workspace, size_t workspace_bytes, double* s_sums, void* stream) {
+  const void* ptrs[] = {sims, workspace, s_sums};
+  if (int e = pw_sync_check(ptrs, 3, batch, n_views, ndepth, height, width, 1L << 62, true, workspace_bytes)) return e;
+  const PwGeo g(batch, n_views, ndepth, height, width);
+  for (int v = 0; v < n_views; ++v) pw_fwd_s_sums(g, sims, v, (double*)workspace, s_sums + 2 * v, (hipStream_t)stream);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
+extern "C" int tmvs_pw_sync_forward_z1(const float* sims, int batch, int n_views, int ndepth, int height, int width,
+                                       const float* pwp, const double* s_sums, long n_total, void* workspace,
+                                       size_t workspace_bytes, float* stats, double* z1_sums, void* stream) {
+  const void* ptrs[] = {sims, pwp, s_sums, workspace, stats, z1_sums};
+  if (int e = pw_sync_check(ptrs, 6, batch, n_views, ndepth, height, width, n_total, true, workspace_bytes)) return e;
+  const PwGeo g(batch, n_views, ndepth, height, width);
+  for (int v = 0; v < n_views; ++v)
+    pw_fwd_z1_sums(g, sims, v, pwp, s_sums + 2 * v, n_total, stats + (size_t)v * 48, (double*)workspace,
+                   z1_sums + 16 * v, (hipStream_t)stream);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
+extern "C" int tmvs_pw_sync_forward_weights(const float* sims, int batch, int n_views, int ndepth, int height,
+                                            int width, const float* pwp, const double* z1_sums, long n_total,
+                                            float* stats, float* view_w, int* dstar, void* stream) {
+  const void* ptrs[] = {sims, pwp, z1_sums, stats, view_w, dstar};
+  if (int e = pw_sync_check(ptrs, 6, batch, n_views, ndepth, height, width, n_total, false, 0)) return e;
+  const PwGeo g(batch, n_views, ndepth, height, width);
+  for (int v = 0; v < n_views; ++v)
+    pw_fwd_weights(g, sims, v, pwp, z1_sums + 16 * v, n_total, stats + (size_t)v * 48, view_w, dstar,
+                   (hipStream_t)stream);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
+extern "C" int tmvs_pw_sync_backward_s1(const float* sims, int batch, int n_views, int ndepth, int height, int width,
+                                        const float* pwp, const float* stats, const float* view_w, const int* dstar,
+                                        const float* dview_w, void* workspace, size_t workspace_bytes, double* s1,
+                                        void* stream) {
+  const void* ptrs[] = {sims, pwp, stats, view_w, dstar, dview_w, workspace, s1};
+  if (int e = pw_sync_check(ptrs, 8, batch, n_views, ndepth, height, width, 1L << 62, true, workspace_bytes)) return e;
+  const PwGeo g(batch, n_views, ndepth, height, width);
+  const PwSaved f{sims, pwp, stats, view_w, dview_w, dstar};
+  for (int v = 0; v < n_views; ++v) pw_bwd_s1(g, f, v, (double*)workspace, s1 + 25 * v, (hipStream_t)stream);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
+extern "C" int tmvs_pw_sync_backward_s2(const float* sims, int batch, int n_views, int ndepth, int height, int width,
+                                        const float* pwp, const float* stats, const float* view_w, const int* dstar,
+                                        const float* dview_w, const double* global_s1, long n_total, void* workspace,
+                                        size_t workspace_bytes, double* s2, void* stream) {
+  const void* ptrs[] = {sims, pwp, stats, view_w, dstar, dview_w, global_s1, workspace, s2};
+  if (int e = pw_sync_check(ptrs, 9, batch, n_views, ndepth, height, width, n_total, true, workspace_bytes)) return e;
+  const PwGeo g(batch, n_views, ndepth, height, width);
+  const PwSaved f{sims, pwp, stats, view_w, dview_w, dstar};
+  for (int v = 0; v < n_views; ++v)
+    pw_bwd_s2(g, f, v, global_s1 + 25 * v, n_total, (double*)workspace, s2 + 160 * v, (hipStream_t)stream);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
+}
+
+extern "C" int tmvs_pw_sync_backward_apply(const float* sims, int batch, int n_views, int ndepth, int height,
+                                           int width, const float* pwp, const float* stats, const float* view_w,
+                                           const int* dstar, const float* dview_w, const double* global_s1,
+                                           const double* global_s2, long n_total, const double* local_s1,
+                                           const double* local_s2, void* workspace, size_t workspace_bytes,
+                                           float* dsims, float* dpwp, void* stream) {
+  const void* ptrs[] = {sims, pwp, stats, view_w, dstar, dview_w, global_s1, global_s2, local_s1, local_s2, workspace,
+                        dsims, dpwp};
+  if (int e = pw_sync_check(ptrs, 13, batch, n_views, ndepth, height, width, n_total, true, workspace_bytes)) return e;
+  hipStream_t st = (hipStream_t)stream;
+  const PwGeo g(batch, n_views, ndepth, height, width);
+  const PwSaved f{sims, pwp, stats, view_w, dview_w, dstar};
+  double* part = (double*)workspace;
+  double* s3 = part + 1024 * 160;
+  for (int v = 0; v < n_views; ++v) {  // the parameter gradients are this rank's: its own s1 / s2 / s3
+    pw_bwd_s3(g, f, v, global_s1 + 25 * v, global_s2 + 160 * v, n_total, dsims, part, s3, st);
+    hipLaunchKernelGGL(pw_grad_finalize_kernel, dim3(1), dim3(128), 0, st, local_s1 + 25 * v, local_s2 + 160 * v,
+                       (const double*)s3, dpwp);
+  }
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
 }

@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import sync_bn
 from .bn_running import update_running_stats
 from .packing import gather_packs
 
@@ -225,9 +226,11 @@ def _untaps(dw, shape):
 class _Tape:
     """What the forward keeps for the backward, and the BatchNorm statistics per view."""
 
-    def __init__(self, n_views):
+    def __init__(self, n_views, sync=None):
         self.n = n_views
-        self.stats = []  # (bn module, (mean [N, C], var [N, C]) per view, pixels per view: B * h * w)
+        self.sync = sync  # sync_bn.SyncBN: the statistics of every view over all ranks (None: this rank's)
+        # (bn module, (mean [N, C], var [N, C]) per view, pixels per view: B * h * w, on all ranks under sync)
+        self.stats = []
 
 
 def _by_view(z, n_views):
@@ -240,17 +243,25 @@ def _bn_relu_views(tape, z, bn):
     """relu(BatchNorm_train(z)) with statistics per view over that view's B images (z [N*B,h,w,C] NHWC,
     view-major): one grouped launch each for the statistics and the normalisation (group = view)."""
     zv = _by_view(z, tape.n)
-    mean, var = ops.bn_stats_grouped(zv)
+    if tape.sync is None:
+        mean, var = ops.bn_stats_grouped(zv)
+        per, n = (mean, var), zv.shape[1]
+    else:  # the same passes with the sums added over ranks in between (sync_bn.py)
+        mean, var, n = sync_bn.bn_stats_grouped(tape.sync, zv)
+        per = (mean, var, tape.sync, n)
     y = ops.bn_relu_train_grouped(zv, mean, var, bn.weight.detach(), bn.bias.detach(), bn.eps).view(z.shape)
-    tape.stats.append((bn, (mean, var), zv.shape[1]))
-    return y, (mean, var)
+    tape.stats.append((bn, (mean, var), n))
+    return y, per
 
 
 def _bn_relu_views_backward(dy, z, per, bn):
-    mean, var = per
+    mean, var, *synced = per
     n = mean.shape[0]
-    dz, dg, db = ops.bn_relu_backward_grouped(_by_view(dy.contiguous(), n), _by_view(z, n), mean, var,
-                                              bn.weight.detach(), bn.bias.detach(), bn.eps)
+    args = (_by_view(dy.contiguous(), n), _by_view(z, n), mean, var, bn.weight.detach(), bn.bias.detach(), bn.eps)
+    if synced:  # (SyncBN, N_total): the collective is issued from inside the backward, as torch's SyncBatchNorm does
+        dz, dg, db = sync_bn.bn_relu_backward_grouped(synced[0], *args, synced[1])
+    else:
+        dz, dg, db = ops.bn_relu_backward_grouped(*args)
     return dz.view(z.shape), dg, db
 
 
@@ -478,11 +489,13 @@ class _FeatureNetTrain(torch.autograd.Function):
         return (None, None, None, *[grads.get(i) for i in ctx.param_ids])
 
 
-def featurenet_train(fnet, imgs):
+def featurenet_train(fnet, imgs, sync=None):
     """FeatureNet.forward in train mode for one sample's views imgs [N,3,H,W] -> (stage1, stage2, stage3)
     NCHW [N,C,h,w], or for a batch imgs [B,N,3,H,W] -> [B,N,C,h,w] each (views of view-major storage);
     differentiable w.r.t. fnet's parameters; updates the BatchNorm running statistics per view as the
-    reference's per-view calls do (models/TransMVSNet.py:151-153: each call sees that view's B images)."""
+    reference's per-view calls do (models/TransMVSNet.py:151-153: each call sees that view's B images).
+    sync (a sync_bn.SyncBN; default: the one of the training forward in progress, sync_bn.current()): every
+    view's statistics over the B images of all ranks, as under nn.SyncBatchNorm."""
     if not imgs.is_cuda:
         raise RuntimeError("featurenet_train runs on the GPU only (no CPU fallback)")
     if imgs.dim() not in (4, 5) or imgs.shape[-3] != 3:
@@ -491,7 +504,8 @@ def featurenet_train(fnet, imgs):
     if batch is not None:  # view-major: view v's B images are rows v*B .. v*B + B - 1
         imgs = imgs.transpose(0, 1).reshape(-1, *imgs.shape[2:])
     n_views = imgs.shape[0] // (batch or 1)
-    tape = _Tape(n_views)
+    sync = sync if sync is not None else sync_bn.current()
+    tape = _Tape(n_views, sync if sync is not None and sync.active else None)
     params = list(fnet.parameters())
     with torch.cuda.device(imgs.device):
         s1, s2, s3 = _FeatureNetTrain.apply(imgs, fnet, tape, *params)

@@ -18,7 +18,8 @@ pyramid comes out of one tmvs_gt_pyramid launch. --batch_size B samples per rank
 train.py's DTU recipe 2): the training order is cut into batches of B with the remainder dropped (the
 reference's train loader has drop_last=True), evaluation runs batches of B with a smaller last one, and every
 train-mode BatchNorm takes its statistics over the batch (train.forward_train). focal_bld takes B = 1 only.
-Not built: apex / --sync_bn (BatchNorm statistics stay per rank), tensorboard summaries, DataParallel,
+--sync_bn under torchrun takes every train-mode BatchNorm statistic over the samples of all ranks (sync_bn.py), as
+the reference always does under torch.distributed. Not built: apex, tensorboard summaries, DataParallel,
 --mode profile.
 """
 from __future__ import annotations
@@ -509,8 +510,8 @@ def make_parser():
     p = argparse.ArgumentParser(
         description="Train / fine-tune TransMVSNet on BlendedMVS or DTU scan folders (HIP training step, "
                     "--batch_size samples per rank and step with BatchNorm statistics over the batch; "
-                    "--loss focal_bld takes --batch_size 1 only). Not built: apex (--using_apex, --sync_bn: "
-                    "BatchNorm statistics stay per rank), tensorboard summaries, DataParallel and --mode "
+                    "--loss focal_bld takes --batch_size 1 only; --sync_bn: those statistics over all ranks). "
+                    "Not built: apex (--using_apex), tensorboard summaries, DataParallel and --mode "
                     "profile; start one process per GPU with torchrun for DDP.")
     p.add_argument("--mode", default="train", choices=["train", "test"], help="train or test")
     p.add_argument("--dataset", default="dtu_yao", choices=sorted(DATASETS), help="select dataset")
@@ -542,6 +543,10 @@ def make_parser():
                    help="auto: focal_bld for bld_train, trans_mvsnet for dtu_yao")
     p.add_argument("--crop", type=str, default="512,640",
                    help="dtu_yao: target_h,target_w of prepare_img's centre crop (the image size)")
+    p.add_argument("--sync_bn", action="store_true",
+                   help="BatchNorm batch statistics over the samples of all ranks (SyncBN). The reference always "
+                        "does this under torch.distributed (convert_sync_batchnorm before DDP); here it is off by "
+                        "default, so runs without the flag keep their bits. A logged no-op with one process")
     p.add_argument("--workers", type=int, default=2, help=f"host decode threads (at most {MAX_WORKERS})")
     return p
 
@@ -631,6 +636,12 @@ def main(argv=None):
                        weight_decay=args.wd)
         if opt_state is not None:
             opt.load_state_dict(opt_state)
+        if args.sync_bn and _is_distributed():
+            model.sync_batchnorm()  # train.py:361-366: convert_sync_batchnorm(model) whenever distributed
+            if main_rank:
+                print("BatchNorm statistics synchronised over {} ranks".format(dist.get_world_size()), flush=True)
+        elif args.sync_bn:
+            print("--sync_bn: one process, nothing to synchronise (statistics are this process's batch)", flush=True)
         if main_rank:
             print("start at epoch {}".format(start_epoch))
             print("Number of model parameters: {}".format(sum(p.numel() for p in model.parameters())), flush=True)

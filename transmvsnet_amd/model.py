@@ -262,7 +262,24 @@ class TransMVSNet(nn.Module):
         # B > 1: one stream per sample (sample 0 on the caller's stream), see _forward_features
         self.batch_streams = True
         self._sample_streams = {}
+        self.sync_bn = None  # sync_batchnorm(): the train-mode BatchNorm statistics over all ranks
         self.register_load_state_dict_post_hook(lambda m, k: m.invalidate())
+
+    def sync_batchnorm(self, group="world", always=False):
+        """Take every train-mode BatchNorm statistic (FeatureNet and PixelwiseNet per view, the CostRegNets) over
+        the samples of all ranks of `group`, with torch.nn.SyncBatchNorm's semantics under DDP; returns self, as
+        the reference's `model = nn.SyncBatchNorm.convert_sync_batchnorm(model)` (train.py:361-366) reads (torch's
+        own conversion has no effect on this model: its train-mode BatchNorm runs in the HIP training Functions,
+        not in the nn.BatchNorm modules' forward). group: a torch.distributed process group, "world" (the
+        default) for the default group, or a ready transmvsnet_amd.sync_bn.SyncBN; sync_batchnorm(None) turns
+        sync off. always: issue the collectives on a one-rank group too (timing, tests). Eval mode is untouched.
+        Refused: a view-sharded forward and HIP-graph capture while sync is on."""
+        from .sync_bn import SyncBN
+        if group is None or isinstance(group, SyncBN):
+            self.sync_bn = group
+        else:
+            self.sync_bn = SyncBN(None if isinstance(group, str) and group == "world" else group, always=always)
+        return self
 
     def _sample_stream(self, dev, i):
         key = (dev, i)
@@ -356,6 +373,9 @@ class TransMVSNet(nn.Module):
         features: per-view list of FeatureNet dicts, or {stage: [B,N,C,h,w]} stacked.
         view_shard: optional transmvsnet_amd.distributed.ViewShard (source views split over ranks).
         """
+        if view_shard is not None and self.sync_bn is not None:
+            from .sync_bn import VIEW_SHARD_MSG
+            raise RuntimeError(VIEW_SHARD_MSG)
         self._check_eval()
         feats = self.stack_features(features)
         if view_shard is not None:  # reference view + this rank's source views only

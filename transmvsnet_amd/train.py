@@ -38,7 +38,7 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import ops, sync_bn
 from .bn_running import update_running_stats
 from .packing import gather_packs
 
@@ -427,7 +427,7 @@ def _down(dhw):
 
 class _CostRegNetTrain(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, eps, stats_out, *params):
+    def forward(ctx, x, eps, stats_out, sync, *params):
         b, d, h, w = x.shape
         ws = params[:-1]
         wprob = params[-1]
@@ -447,15 +447,21 @@ class _CostRegNetTrain(torch.autograd.Function):
             cout = wt.shape[1] if transposed else wt.shape[0]
             odims = tuple(2 * n for n in dims) if transposed else (dims if stride == 1 else _down(dims))
             z = _conv_fwd(cur, fwd_pk[i], cout, odims, stride, transposed)
-            mean, var = ops.bn_stats(z)
+            if sync is None:
+                mean, var = ops.bn_stats(z)
+                n = z.numel() // z.shape[-1]
+            else:  # one group: the statistics over the voxels of all ranks (sync_bn.py)
+                mean, var, n = sync_bn.bn_stats_grouped(sync, z.view(1, -1, cout))
+                mean, var = mean[0], var[0]
             y = ops.bn_relu_train(z, mean, var, g.detach(), bt.detach(), eps,
                                   skip=acts[skip][0] if skip is not None else None)
-            saved.append((cur, dims, z, mean, var))
-            stats.append((mean, var, z.numel() // z.shape[-1]))
+            saved.append((cur, dims, z, mean, var, n))
+            stats.append((mean, var, n))
             acts[name] = (y, odims)
             cur, dims = y, odims
         logits = _conv_fwd(cur, fwd_pk[-1], 1, dims, 1, False)
         ctx.eps = eps
+        ctx.sync = sync
         ctx.layer_io = saved
         ctx.u11 = cur
         stats_out.extend(stats)
@@ -477,12 +483,18 @@ class _CostRegNetTrain(torch.autograd.Function):
         for i in range(len(_LAYERS) - 1, -1, -1):
             name, stride, transposed, skip = _LAYERS[i]
             wt, gm, bt = ws[3 * i], ws[3 * i + 1], ws[3 * i + 2]
-            xin, idims, z, mean, var = ctx.layer_io[i]
+            xin, idims, z, mean, var, n = ctx.layer_io[i]
             dy = dout.pop(name)
             if skip is not None:  # y = skip + relu(bn(z)): the skip source receives dy as is (aliased: dy is
                 # only read again by bn_relu_backward below, stream-ordered before any in-place accumulation)
                 dout[skip] = dy if skip not in dout else dout[skip].add_(dy)
-            dz, dgam, dbet = ops.bn_relu_backward(dy, z, mean, var, gm.detach(), bt.detach(), eps)
+            if ctx.sync is None:
+                dz, dgam, dbet = ops.bn_relu_backward(dy, z, mean, var, gm.detach(), bt.detach(), eps)
+            else:  # the collective from inside the backward, as torch's SyncBatchNorm issues it
+                dz, dgam, dbet = sync_bn.bn_relu_backward_grouped(
+                    ctx.sync, dy.view(1, -1, z.shape[-1]), z.view(1, -1, z.shape[-1]), mean[None], var[None],
+                    gm.detach(), bt.detach(), eps, n)
+                dz = dz.view(z.shape)
             if transposed:
                 dw = ops.conv3d_wgrad(xin, dz, 2)
             else:
@@ -502,7 +514,7 @@ class _CostRegNetTrain(torch.autograd.Function):
         grads[-1] = unp[-1]
         ctx.dgrad_pk = None
         dx = dout["input"].view(b, d, h, w)
-        return (dx, None, None, *grads)
+        return (dx, None, None, None, *grads)
 
 
 def costregnet_params(module):
@@ -515,9 +527,11 @@ def costregnet_params(module):
     return ps + [module.prob.weight]
 
 
-def costregnet_train(module, x):
+def costregnet_train(module, x, sync=None):
     """CostRegNet.forward in train mode on the HIP kernels; differentiable w.r.t. x and the module's
-    parameters; updates the BatchNorm running statistics like nn.BatchNorm3d (momentum 0.1)."""
+    parameters; updates the BatchNorm running statistics like nn.BatchNorm3d (momentum 0.1). sync (a
+    sync_bn.SyncBN; default sync_bn.current()): batch statistics over the voxels of all ranks, and the
+    running statistics from them with the global count."""
     if not x.is_cuda:
         raise RuntimeError("costregnet_train runs on the GPU only (no CPU fallback)")
     if x.dim() != 4 or any(n % 8 for n in x.shape[1:]):
@@ -526,7 +540,7 @@ def costregnet_train(module, x):
     params = costregnet_params(module)
     stats = []
     with torch.cuda.device(x.device):
-        logits = _CostRegNetTrain.apply(x.float(), eps, stats, *params)
+        logits = _CostRegNetTrain.apply(x.float(), eps, stats, _active_sync(sync), *params)
         update_running_stats([(getattr(module, name).bn, mean[None], var[None], n)
                               for (name, _, _, _), (mean, var, n) in zip(_LAYERS, stats)], BN_MOMENTUM)
     return logits
@@ -541,14 +555,18 @@ class _AggregateTrain(torch.autograd.Function):
     as the reference returns them detached)."""
 
     @staticmethod
-    def forward(ctx, sims, pwp, vw_given, vw_shift, stats_out):
+    def forward(ctx, sims, pwp, vw_given, vw_shift, stats_out, sync):
         sims = sims.contiguous()
         single = sims.dim() == 4
         sb = sims[None] if single else sims
         b, v, d, h, w = sb.shape
-        if vw_given is None:
+        if vw_given is None and sync is not None:  # the staged passes, their sums added over ranks (sync_bn.py)
+            stats, vw, dstar, n_total = sync_bn.pixelwise_forward(sync, sb, pwp.detach().contiguous())
+            stats_out.append((stats, n_total))
+            ctx.pw = (stats, dstar, sync, n_total)
+        elif vw_given is None:
             stats, vw, dstar = ops.pixelwise_train_forward_batched(sb, pwp.detach().contiguous())
-            stats_out.append(stats)
+            stats_out.append((stats, b * d * h * w))
             ctx.pw = (stats, dstar)
         else:
             vw = vw_given.contiguous()
@@ -575,9 +593,13 @@ class _AggregateTrain(torch.autograd.Function):
                                          dview_w=dvw[i] if stage1 else None)
         dpwp = None
         if stage1:
-            stats, dstar = ctx.pw
-            dpwp = ops.pixelwise_train_backward_batched(sb, pwp.detach().contiguous(), stats, vw, dstar, dvw, dsims)
-        return (dsims[0] if ctx.single else dsims), dpwp, None, None, None
+            stats, dstar, *synced = ctx.pw
+            if synced:
+                dpwp = sync_bn.pixelwise_backward(synced[0], sb, pwp.detach().contiguous(), stats, vw, dstar, dvw,
+                                                  dsims, synced[1])
+            else:
+                dpwp = ops.pixelwise_train_backward_batched(sb, pwp.detach().contiguous(), stats, vw, dstar, dvw, dsims)
+        return (dsims[0] if ctx.single else dsims), dpwp, None, None, None, None
 
 
 def _pw_params(pw):
@@ -587,21 +609,28 @@ def _pw_params(pw):
                       pw.conv2.weight.reshape(8), pw.conv2.bias.reshape(1)]).float()
 
 
-def aggregate_train(sims, model, vw_given=None, vw_shift=0):
+def _active_sync(sync=None):
+    """the SyncBN a training Function runs under: the one given, else the training forward's (sync_bn.using);
+    None unless it communicates"""
+    sync = sync if sync is not None else sync_bn.current()
+    return sync if sync is not None and sync.active else None
+
+
+def aggregate_train(sims, model, vw_given=None, vw_shift=0, sync=None):
     """DepthNet's view aggregation for training; at stage 1 (vw_given None) the view weights come
     from PixelwiseNet in train mode, whose BatchNorm running statistics are updated once per view
     (the reference calls it per view). sims [V,D,H,W] -> (sim [D,H,W], view weights [V,H',W']); a batch
     sims [B,V,D,H,W] -> (sim [B,D,H,W], view weights [B,V,H',W']) with the PixelwiseNet statistics, and the
     n of the unbiased running variance, over the B*D*H*W elements of each view (TransMVSNet.py:71-77 runs
-    it on [B,1,D,h,w])."""
+    it on [B,1,D,h,w]). sync (a sync_bn.SyncBN; default sync_bn.current()): those statistics, and that n, over
+    all ranks."""
     pw = model.DepthNet.pixel_wise_net
     if sims.dim() not in (4, 5):
         raise ValueError(f"aggregate_train: sims must be [V,D,H,W] or [B,V,D,H,W], not {list(sims.shape)}")
     stats = []
-    sim, vw = _AggregateTrain.apply(sims, _pw_params(pw), vw_given, vw_shift, stats)
+    sim, vw = _AggregateTrain.apply(sims, _pw_params(pw), vw_given, vw_shift, stats, _active_sync(sync))
     if stats:
-        n = sims.numel() // sims.shape[-4]  # elements per view: (B *) D * H * W
-        st = stats[0]  # [views, 48], views in order
+        st, n = stats[0]  # [views, 48], views in order; elements per view: (B *) D * H * W (of all ranks under sync)
         update_running_stats([(pw.conv0.bn, st[:, 0:16], st[:, 16:32], n), (pw.conv1.bn, st[:, 32:40], st[:, 40:48], n)],
                              pw.conv0.bn.momentum)
     return sim, vw
@@ -648,7 +677,7 @@ def depth_stages_forward_train(model, stage_features, proj_matrix, depth_values,
     if depth_values.shape[0] != b or any(proj_matrix[f"stage{s + 1}"].shape[0] != b for s in range(3)):
         raise ValueError(f"depth_stages_forward_train: {b} sample(s) of features, but depth_values "
                          f"{list(depth_values.shape)} and proj_matrix {list(proj_matrix['stage1'].shape)}")
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), sync_bn.using(getattr(model, "sync_bn", None) or sync_bn.current()):
         dv = depth_values.to(dev, torch.float32).contiguous()
         outputs, prev_raw, vw_det = {}, None, None
         for s in range(3):
@@ -740,7 +769,12 @@ def forward_train(model, imgs, proj_matrix, depth_values):
     if not imgs.is_cuda:
         raise RuntimeError("TransMVSNet (HIP) needs GPU inputs; the HIP path has no CPU fallback")
     h, w = imgs.shape[3], imgs.shape[4]
-    with torch.cuda.device(imgs.device):
+    with torch.cuda.device(imgs.device), sync_bn.using(getattr(model, "sync_bn", None)) as sync:
+        if sync is not None:  # the sums of all ranks are divided by world * this rank's count
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(sync_bn.CAPTURE_MSG)
+            sync.begin_step()
+            sync.check_counts(tuple(imgs.shape), device=imgs.device)
         s1, s2, s3 = featurenet_train(model.feature, imgs[0] if imgs.shape[0] == 1 else imgs)
         st1 = fmt_train(model, s1)
         st2, st3 = pathway_train(model, st1, s2, s3)
@@ -972,6 +1006,8 @@ class TrainStepGraph:
     be warm before capture: run the step once eagerly first (capture raises otherwise)."""
 
     def __init__(self, fn, model, stream=None):
+        if getattr(model, "sync_bn", None) is not None:
+            raise RuntimeError(sync_bn.CAPTURE_MSG)
         self.model = model
         self.graph = torch.cuda.CUDAGraph()
         dev = next(model.parameters()).device
