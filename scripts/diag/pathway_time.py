@@ -1,8 +1,10 @@
 """The FMT pathway launches alone (no concurrent stage-1 kernels), DTU full size, HIP-event medians.
 
     python scripts/diag/pathway_time.py [REPS]          (TMVS_LIB_PATH selects a library variant)
-Prints the stage-2 (32 -> 16, `tmvs_fmt_pathway` cc=32) and stage-3 (16 -> 8) per-launch medians.
+Prints the stage-2 (32 -> 16, `tmvs_fmt_pathway` cc=32) and stage-3 (16 -> 8) per-launch medians and a bit-level
+digest of each stage's output (A/B builds must print the same digests).
 """
+import hashlib
 import os
 import sys
 
@@ -39,6 +41,8 @@ def med(fn):
 
 out2 = ops.fmt_pathway(st1, s2, prep["red1"], prep["sm1"])
 t2 = med(lambda: ops.fmt_pathway(st1, s2, prep["red1"], prep["sm1"]))
+out3 = ops.fmt_pathway(out2, s3, prep["red2"], prep["sm2"])
 t3 = med(lambda: ops.fmt_pathway(out2, s3, prep["red2"], prep["sm2"]))
-print(f"pathway {os.environ.get('TMVS_LIB_PATH', 'default')}: stage 2 {t2:.1f} us, stage 3 {t3:.1f} us, "
-      f"stage-2 checksum {float(out2.double().sum()):.9e}")
+d2, d3 = (hashlib.sha1(o.cpu().numpy().tobytes()).hexdigest()[:16] for o in (out2, out3))
+print(f"pathway {os.environ.get('TMVS_LIB_PATH', 'default')}: stage 2 {t2:.1f} us, stage 3 {t3:.1f} us | "
+      f"stage 2 {d2} stage 3 {d3}", flush=True)

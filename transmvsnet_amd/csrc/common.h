@@ -20,9 +20,43 @@
 
 namespace tmvs {
 
-constexpr int kWave = 64;
-
 __device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
+
+typedef float floatx4_t __attribute__((ext_vector_type(4)));  // an MFMA accumulator / one 16-byte buffer load
+
+// One axis of torch's bilinear interpolation with align_corners=False (area_pixel_compute_source_index +
+// guard_index_and_lambda): output index dst of out_size reads in[i0] * l0 + in[i1] * l1. The callers keep
+// their own interpolation arithmetic (fmaf chains in the inference kernels, as torch's CPU kernels contract).
+struct LinAxis {
+  int i0, i1;
+  float l0, l1;
+};
+__device__ __forceinline__ LinAxis lin_axis(int dst, int in_size, int out_size) {
+  const float scale = (float)in_size / (float)out_size;
+  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  LinAxis a;
+  a.i0 = min((int)floorf(src), in_size - 1);
+  a.i1 = a.i0 + (a.i0 < in_size - 1 ? 1 : 0);
+  const float l = fminf(fmaxf(src - (float)a.i0, 0.f), 1.f);
+  a.l1 = l;
+  a.l0 = 1.f - l;
+  return a;
+}
+// The same bits for out_size = 2 in_size, without what that case never needs: in / (2 in) is exactly 0.5,
+// src >= 0 so truncation is floor, and src <= in - 0.75 so l is 0, 0.25 or 0.75 and its clamp never acts.
+// The training kernels use it: through lin_axis, upsample2_add_kernel<16> took 26.9 us against 25.7.
+__device__ __forceinline__ LinAxis lin_axis_x2(int dst, int in_size) {
+  float src = 0.5f * ((float)dst + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  LinAxis a;
+  a.i0 = (int)src;
+  a.i0 = a.i0 < in_size - 1 ? a.i0 : in_size - 1;
+  a.i1 = a.i0 + (a.i0 < in_size - 1 ? 1 : 0);
+  a.l1 = src - (float)a.i0;
+  a.l0 = 1.f - a.l1;
+  return a;
+}
 
 // Bijective XCD-aware block remap (cdna_hip_programming.md T1): blocks b and b+8 share
 // an XCD, so give each XCD a contiguous chunk of the tile space.
@@ -150,7 +184,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void* base, uns
 __device__ __forceinline__ float buf_load_f32(__amdgpu_buffer_rsrc_t r, unsigned off) {
   return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));  // returns the raw bits
 }
-typedef float floatx4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ floatx4_t buf_load_f32x4(__amdgpu_buffer_rsrc_t r, unsigned off) {
   return __builtin_bit_cast(floatx4_t, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
 }

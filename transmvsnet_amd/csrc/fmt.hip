@@ -11,68 +11,25 @@
 //                     msg = (Q·KV) Z, x = LN1(x + Wo msg + bo), x = LN2(x + W2 relu(W1 x + b1) + b2)
 // Cross layers read the reference view's (KV, Ksum) for every source view (kv stride 0):
 // the reference recomputes the identical values per view (FMT.py:170-176).
-// The 8.5 KMAC/token of weights are wave-uniform: the compiler streams them through the
-// scalar cache (s_load) as SGPR operands of v_fma_f32, so the VALU runs at full rate.
-#include "common.h"
+//
+// The token-wise linears are dense 32x32 / 32x64 / 64x32 GEMMs over tiles of 16 tokens on the
+// exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32: D = A.B + C as an fp32 FMA chain, the VALU
+// fp32 rate):
+//   D[o][t] = sum_k W[o][k] X[t][k]   A = W (16 outputs x 4 k),  B = X^T (4 k x 16 tokens)
+// The weights are staged once per workgroup into LDS as A fragments in read order (stage_afrag)
+// and read back inside the tile loop, one ds_read_b128 per 4 k-steps; the tokens and every
+// intermediate stay in registers.
+// Lane l holds D[o = 16mb + 4(l>>4) + r][t = l&15]: a token's 32 features live in lanes
+// t, t+16, t+32, t+48 (8 each), and head h = 4mb + (l>>4) is lane-local (4 consecutive features).
+// K-step s of a linear takes, in lane group g = l>>4, input feature kfeat(s, g) = 16(s>>2) + 4g + (s&3):
+// exactly the register (mb = s>>2, r = s&3) that lane already holds from the previous linear's
+// accumulator -- so the linears chain with no data movement. Within a chain the input features
+// are summed in that permuted order (an exact fp32 FMA chain; the reference's BLAS order is
+// unknown anyway). History: the VALU version was bound by weight delivery (PMC); with
+// the A fragments resident in VGPRs (96 of them) the apply was capped at 2 waves/SIMD.
+#include "fmt_common.h"
 
 namespace tmvs {
-
-constexpr int kD = 32;
-constexpr int kKV = TMVS_KV_NFLOATS;
-constexpr int kKvBlock = 256;
-
-__device__ __forceinline__ float elu1(float x) { return (x > 0.f ? x : expm1f(x)) + 1.f; }
-
-__device__ __forceinline__ void load_token(const float* __restrict__ p, float (&x)[kD]) {
-#pragma unroll
-  for (int c4 = 0; c4 < kD / 4; ++c4) {
-    const float4 t = *reinterpret_cast<const float4*>(p + c4 * 4);
-    x[c4 * 4 + 0] = t.x;
-    x[c4 * 4 + 1] = t.y;
-    x[c4 * 4 + 2] = t.z;
-    x[c4 * 4 + 3] = t.w;
-  }
-}
-
-// F.linear (addmm) y = x·W^T + b with W stored transposed ([in][out]): for each input i the
-// OUT consecutive weights of row i arrive as one scalar load (SGPR operands of v_fma_f32) and
-// are accumulated into y[0..OUT) -- per output an FMA chain over the input index, in order.
-template <int IN, int OUT>
-__device__ __forceinline__ void linear_t(const float* __restrict__ WT, const float* __restrict__ b, const float* x,
-                                         float* y) {
-#pragma unroll
-  for (int o = 0; o < OUT; ++o) y[o] = 0.f;
-#pragma unroll 2
-  for (int i = 0; i < IN; ++i)
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) y[o] = fmaf(WT[i * OUT + o], x[i], y[o]);
-#pragma unroll
-  for (int o = 0; o < OUT; ++o) y[o] = y[o] + b[o];
-}
-
-// Layer weights are staged once per workgroup into LDS (34 KB) and read back as wave-uniform
-// (broadcast) LDS loads; streaming them through the scalar cache from every wave thrashes it.
-__device__ __forceinline__ void stage_weights(float* __restrict__ lds, const float* __restrict__ w, int n) {
-  for (int i = threadIdx.x * 4; i < n; i += blockDim.x * 4)
-    *reinterpret_cast<float4*>(lds + i) = *reinterpret_cast<const float4*>(w + i);
-}
-
-__device__ __forceinline__ void layer_norm(float (&x)[kD], const float* __restrict__ g, const float* __restrict__ b) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < kD; ++i) s += x[i];
-  const float mean = s / (float)kD;
-  float v = 0.f;
-#pragma unroll
-  for (int i = 0; i < kD; ++i) {
-    const float d = x[i] - mean;
-    v = fmaf(d, d, v);
-  }
-  const float rstd = 1.f / sqrtf(v / (float)kD + 1e-5f);
-  const float bias = -rstd * mean;
-#pragma unroll
-  for (int i = 0; i < kD; ++i) x[i] = fmaf(fmaf(x[i], rstd, bias), g[i], b[i]);
-}
 
 // tokens[v][p][c] = feat[v][c][p] + pe[c][y][x]: a block transposes 64 pixels x 32 channels through
 // LDS for every view (coalesced 256-B channel rows in, 8 KB of contiguous token rows out), reading
@@ -115,52 +72,12 @@ __global__ __launch_bounds__(256) void fmt_embed_kernel(const float* __restrict_
   }
 }
 
-// ============================================================================ MFMA formulation
-// The token-wise linears are dense 32x32 / 32x64 / 64x32 GEMMs over tokens. They run on the
-// exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32: D = A.B + C as an fp32 FMA chain, the VALU
-// fp32 rate) with the weights resident in VGPRs as A fragments, loaded once per wave:
-//   D[o][t] = sum_k W[o][k] X[t][k]   A = W (16 outputs x 4 k),  B = X^T (4 k x 16 tokens)
-// Lane l holds D[o = 16mb + 4(l>>4) + r][t = l&15]: a token's 32 features live in lanes
-// t, t+16, t+32, t+48 (8 each), and head h = 4mb + (l>>4) is lane-local (4 consecutive features).
-// K-step s of a linear takes, in lane group g = l>>4, input feature f(s,g) = 16(s>>2) + 4g + (s&3):
-// exactly the register (mb = s>>2, r = s&3) that lane already holds from the previous linear's
-// accumulator -- so the linears chain with no data movement. Within a chain the input features
-// are summed in that permuted order (an exact fp32 FMA chain; the reference's BLAS order is
-// unknown anyway). VALU version of this file's history: bound by weight delivery (PMC).
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ int kfeat(int s, int g) { return 16 * (s >> 2) + 4 * g + (s & 3); }
 
-// A fragments of a [OUT][IN] linear: frag[mb][s] = W[16mb + (l&15)][kfeat(s, l>>4)].
-// TRANS: the packed matrix is stored [IN][OUT].
-template <int OUT, int IN, bool TRANS>
-__device__ __forceinline__ void load_afrag(const float* __restrict__ W, float (&frag)[OUT / 16][IN / 4], int lane) {
-#pragma unroll
-  for (int mb = 0; mb < OUT / 16; ++mb)
-#pragma unroll
-    for (int s = 0; s < IN / 4; ++s) {
-      const int o = 16 * mb + (lane & 15), i = kfeat(s, lane >> 4);
-      frag[mb][s] = TRANS ? W[i * OUT + o] : W[o * IN + i];
-    }
-}
-
-// acc[mb] = sum_s A[mb][s] * in[s>>2][s&3]  (in: the B operand registers, D-layout of the input)
-template <int OUT, int IN>
-__device__ __forceinline__ void mfma_linear(const float (&frag)[OUT / 16][IN / 4], const floatx4 (&in)[IN / 16],
-                                            floatx4 (&acc)[OUT / 16]) {
-#pragma unroll
-  for (int mb = 0; mb < OUT / 16; ++mb) acc[mb] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < IN / 4; ++s)
-#pragma unroll
-    for (int mb = 0; mb < OUT / 16; ++mb)
-      acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(frag[mb][s], in[s >> 2][s & 3], acc[mb], 0, 0, 0);
-}
-
-// A fragments staged in LDS in read order [mb][s/4][lane][4]: one ds_read_b128 per lane
-// serves 4 consecutive k-steps of an MFMA chain, and the 64 lanes read 1 KiB contiguous
-// (conflict-free). Used by fmt_apply_kernel, whose 96 weight VGPRs otherwise capped it at
-// 2 waves/SIMD.
+// A fragments of a [OUT][IN] linear (TRANS: the packed matrix is stored [IN][OUT]), staged in LDS in
+// read order [mb][s/4][lane][4] with element (mb, s, l) = W[16mb + (l&15)][kfeat(s, l>>4)]: one
+// ds_read_b128 per lane serves 4 consecutive k-steps of an MFMA chain, and the 64 lanes read 1 KiB
+// contiguous (conflict-free).
 template <int OUT, int IN, bool TRANS>
 __device__ __forceinline__ void stage_afrag(const float* __restrict__ W, float* __restrict__ lds) {
   constexpr int N = OUT * IN;  // = (OUT/16) * (IN/16) * 64 lanes * 4
@@ -173,47 +90,52 @@ __device__ __forceinline__ void stage_afrag(const float* __restrict__ W, float* 
   }
 }
 
-template <int OUT, int IN, int NT>
-__device__ __forceinline__ void mfma_linear_lds(const float* __restrict__ fl, const floatx4 (&in)[NT][IN / 16],
-                                                floatx4 (&acc)[NT][OUT / 16], int lane) {
+// acc[mb] = sum_s A[mb][s] * in[s>>2][s&3] for one tile (in: the B operand registers, the D layout of
+// the input), A from the LDS fragments fl
+template <int OUT, int IN>
+__device__ __forceinline__ void mfma_linear_lds(const float* __restrict__ fl, const floatx4_t (&in)[IN / 16],
+                                                floatx4_t (&acc)[OUT / 16], int lane) {
 #pragma unroll
-  for (int p = 0; p < NT; ++p)
-#pragma unroll
-    for (int mb = 0; mb < OUT / 16; ++mb) acc[p][mb] = floatx4{0.f, 0.f, 0.f, 0.f};
+  for (int mb = 0; mb < OUT / 16; ++mb) acc[mb] = floatx4_t{0.f, 0.f, 0.f, 0.f};
   // per s4: every output block's fragment first, then the MFMAs block-interleaved (each accumulator's
   // own order unchanged), so consecutive MFMAs feed different accumulators
 #pragma unroll
   for (int s4 = 0; s4 < IN / 16; ++s4) {
     float4 a4[OUT / 16];
 #pragma unroll
-    for (int mb = 0; mb < OUT / 16; ++mb)
-      a4[mb] = *reinterpret_cast<const float4*>(fl + ((mb * (IN / 16) + s4) * 64 + lane) * 4);
+    for (int mb = 0; mb < OUT / 16; ++mb) a4[mb] = ld4(fl + ((mb * (IN / 16) + s4) * 64 + lane) * 4);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int mb = 0; mb < OUT / 16; ++mb)
-#pragma unroll
-        for (int p = 0; p < NT; ++p)
-          acc[p][mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(j == 0 ? a4[mb].x : j == 1 ? a4[mb].y : j == 2 ? a4[mb].z : a4[mb].w,
-                                                            in[p][s4][j], acc[p][mb], 0, 0, 0);
+        acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(j == 0 ? a4[mb].x : j == 1 ? a4[mb].y : j == 2 ? a4[mb].z : a4[mb].w,
+                                                       in[s4][j], acc[mb], 0, 0, 0);
   }
 }
 
-// NT independent tiles interleaved: NT x OUT/16 independent accumulation chains in flight
-template <int OUT, int IN, int NT>
-__device__ __forceinline__ void mfma_linear_n(const float (&frag)[OUT / 16][IN / 4], const floatx4 (&in)[NT][IN / 16],
-                                              floatx4 (&acc)[NT][OUT / 16]) {
-#pragma unroll
-  for (int p = 0; p < NT; ++p)
-#pragma unroll
-    for (int mb = 0; mb < OUT / 16; ++mb) acc[p][mb] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < IN / 4; ++s)
-#pragma unroll
-    for (int p = 0; p < NT; ++p)
-#pragma unroll
-      for (int mb = 0; mb < OUT / 16; ++mb)
-        acc[p][mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(frag[mb][s], in[p][s >> 2][s & 3], acc[p][mb], 0, 0, 0);
+// What the two tile-walking kernels (fmt_kv_partial_kernel, fmt_apply_kernel) share: 4 waves per
+// block, wave wv of block b walks tpw tiles of 16 tokens from tile (4b + wv) tpw.
+//
+// the wave index, wave-uniform (readfirstlane): the tile loop is then scalar control flow, not a divergent
+// loop whose per-lane exits make the compiler wait vmcnt(0) (stores included) at its head
+__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+__device__ __forceinline__ int first_tile(int wv, int tpw) { return (blockIdx.x * 4 + wv) * tpw; }
+// an opaque 0 to offset LDS pointers by: the fragment reads stay in the loop (not hoisted back into VGPRs).
+// An SGPR: a VGPR here could alias a pending load (vmcnt wait)
+__device__ __forceinline__ int opaque_zero() {
+  int salt = 0;
+  asm volatile("" : "+s"(salt));
+  return salt;
+}
+// token t's row of an [n][32] view, clamped to the last one: the next tile is prefetched unconditionally
+// (past the wave's range the value is never used) -- a branch there made the compiler wait vmcnt(0) for
+// the prefetch before the tile's first MFMA
+template <typename T>
+__device__ __forceinline__ T* row(T* base, int t, int n) { return base + (size_t)(t < n ? t : n - 1) * kD; }
+// one 16-byte (LDS) read as four scalars
+__device__ __forceinline__ void ld4(const float* p, float (&a)[4]) {
+  const float4 t = ld4(p);
+  a[0] = t.x, a[1] = t.y, a[2] = t.z, a[3] = t.w;
 }
 
 // a token's 32 features are spread over lanes t, t+16, t+32, t+48 (8 per lane)
@@ -223,7 +145,7 @@ __device__ __forceinline__ float token_sum(float v) {
   return v;
 }
 
-__device__ __forceinline__ void layer_norm_frag(floatx4 (&x)[2], const float* __restrict__ g,
+__device__ __forceinline__ void layer_norm_frag(floatx4_t (&x)[2], const float* __restrict__ g,
                                                 const float* __restrict__ b, int lane) {
   float s = 0.f;
 #pragma unroll
@@ -239,44 +161,37 @@ __device__ __forceinline__ void layer_norm_frag(floatx4 (&x)[2], const float* __
       const float d = x[mb][r] - mean;
       v = fmaf(d, d, v);
     }
-  const float rstd = 1.f / sqrtf(token_sum(v) / (float)kD + 1e-5f);
+  const float rstd = 1.f / sqrtf(token_sum(v) / (float)kD + kLnEps);
   const float bias = -rstd * mean;
 #pragma unroll
   for (int mb = 0; mb < 2; ++mb) {
     // features 16 mb + 4 (lane >> 4) + r, r < 4: one 16-byte read each of gamma and beta (aligned)
-    const float4 g4 = *reinterpret_cast<const float4*>(g + 16 * mb + 4 * (lane >> 4));
-    const float4 b4 = *reinterpret_cast<const float4*>(b + 16 * mb + 4 * (lane >> 4));
-    const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
+    float gg[4], bb[4];
+    ld4(g + 16 * mb + 4 * (lane >> 4), gg);
+    ld4(b + 16 * mb + 4 * (lane >> 4), bb);
 #pragma unroll
     for (int r = 0; r < 4; ++r) x[mb][r] = fmaf(fmaf(x[mb][r], rstd, bias), gg[r], bb[r]);
   }
 }
 
-__device__ __forceinline__ void load_token_frag(const float* __restrict__ row, floatx4 (&x)[2], int lane) {
+__device__ __forceinline__ void load_token_frag(const float* __restrict__ row, floatx4_t (&x)[2], int lane) {
 #pragma unroll
   for (int mb = 0; mb < 2; ++mb) {
-    const float4 t = *reinterpret_cast<const float4*>(row + 16 * mb + 4 * (lane >> 4));
-    x[mb] = floatx4{t.x, t.y, t.z, t.w};
+    const float4 t = ld4(row + 16 * mb + 4 * (lane >> 4));
+    x[mb] = floatx4_t{t.x, t.y, t.z, t.w};
   }
 }
 
 constexpr int kKvTilesPerWave = 8;     // kv: at most this many tiles per wave (see kv_tiles_per_wave)
 
 // x + x[lane ^ 1], then ^2, ^4, ^8: the butterfly sum over a 16-lane row. The partner values move by
-// DPP (quad_perm for 1 and 2; row_half_mirror = ^7 and row_mirror = ^15 composed with a quad_perm /
-// half mirror for 4 and 8), not by ds_bpermute through the LDS unit: the same values in the same
+// DPP (xor_lane_dpp, common.h), not by ds_bpermute through the LDS unit: the same values in the same
 // additions, so the sums are bitwise those of __shfl_xor.
-template <int CTRL>
-__device__ __forceinline__ float dppf(float x) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), CTRL, 0xF, 0xF, false));
+template <int OFF>
+__device__ __forceinline__ float xor_add(float x) {
+  return x + __int_as_float(xor_lane_dpp<OFF>(__float_as_int(x)));
 }
-__device__ __forceinline__ float xor_sum16(float x) {
-  x += dppf<0xB1>(x);               // quad_perm [1,0,3,2]: lane ^ 1
-  x += dppf<0x4E>(x);               // quad_perm [2,3,0,1]: lane ^ 2
-  x += dppf<0x1B>(dppf<0x141>(x));  // half mirror (^7) then quad_perm [3,2,1,0] (^3): lane ^ 4
-  x += dppf<0x141>(dppf<0x140>(x)); // row mirror (^15) then half mirror (^7): lane ^ 8
-  return x;
-}
+__device__ __forceinline__ float xor_sum16(float x) { return xor_add<8>(xor_add<4>(xor_add<2>(xor_add<1>(x)))); }
 
 // (KV, Ksum) partial sums: per wave, tiles of 16 source tokens; K, V by MFMA; per lane the
 // two heads it owns are accumulated over its tokens, then summed over the 16 token lanes.
@@ -286,9 +201,7 @@ __global__ __launch_bounds__(256) void fmt_kv_partial_kernel(const float* __rest
   __shared__ float red[4][kKV];
   __shared__ __attribute__((aligned(16))) float frag[2 * 32 * 32];  // Wk, Wv fragments (see stage_afrag)
   const int v = blockIdx.y;
-  // wave index wave-uniform (readfirstlane): the tile loop is then scalar control flow, not a divergent
-  // loop whose per-lane exits make the compiler wait vmcnt(0) (stores included) at its head
-  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, wv = wave_index();
   const int g = lane >> 4;
   stage_afrag<32, 32, true>(w + TMVS_ENC_WK, frag);
   stage_afrag<32, 32, true>(w + TMVS_ENC_WV, frag + 1024);
@@ -310,40 +223,25 @@ __global__ __launch_bounds__(256) void fmt_kv_partial_kernel(const float* __rest
   }
   __syncthreads();
   const float* sv = src + (size_t)v * S * kD;
-  const int tile0 = (blockIdx.x * 4 + wv) * tpw;
-  floatx4 xa[2], xb[2];  // this tile's tokens, the next tile's (loaded while this one computes)
-  if (tile0 * 16 < S) {
-    const int t = tile0 * 16 + (lane & 15);
-    load_token_frag(sv + (size_t)(t < S ? t : S - 1) * kD, xa, lane);
-  }
-  auto tile = [&](int it, floatx4 (&cur)[2], floatx4 (&nxt)[2]) {
-    int salt = 0;  // opaque offset: fragment reads stay in the loop (not hoisted back into VGPRs)
-    asm volatile("" : "+s"(salt));  // an SGPR: a VGPR here could alias a pending load (vmcnt wait)
-    const float* fr = frag + salt;
-    bool okp[1];
-    floatx4 xin[1][2], kk[1][2], vv[1][2];
-    {
-      const int t = (tile0 + it) * 16 + (lane & 15);
-      okp[0] = t < S;
-      xin[0][0] = cur[0];
-      xin[0][1] = cur[1];
-      // unconditional (clamped row; past the wave's range the value is never used): a branch here
-      // made the compiler wait vmcnt(0) for this prefetch before the tile's first MFMA
-      const int tn = t + 16;
-      load_token_frag(sv + (size_t)(tn < S ? tn : S - 1) * kD, nxt, lane);
-    }
-    mfma_linear_lds<32, 32, 1>(fr, xin, kk, lane);
-    mfma_linear_lds<32, 32, 1>(fr + 1024, xin, vv, lane);
-#pragma unroll
-    for (int p = 0; p < 1; ++p)
+  const int tile0 = first_tile(wv, tpw);
+  floatx4_t xa[2], xb[2];  // this tile's tokens, the next tile's (loaded while this one computes)
+  if (tile0 * 16 < S) load_token_frag(row(sv, tile0 * 16 + (lane & 15), S), xa, lane);
+  auto tile = [&](int it, floatx4_t (&cur)[2], floatx4_t (&nxt)[2]) {
+    const float* fr = frag + opaque_zero();
+    const int t = (tile0 + it) * 16 + (lane & 15);
+    const bool ok = t < S;
+    const floatx4_t xin[2] = {cur[0], cur[1]};
+    floatx4_t kk[2], vv[2];
+    load_token_frag(row(sv, t + 16, S), nxt, lane);
+    mfma_linear_lds<32, 32>(fr, xin, kk, lane);
+    mfma_linear_lds<32, 32>(fr + 1024, xin, vv, lane);
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb) {
-      const bool ok = okp[p];
       float kh[4], vh[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        kh[r] = ok ? elu1(kk[p][mb][r] + bk[mb][r]) : 0.f;
-        vh[r] = ok ? vv[p][mb][r] + bv[mb][r] : 0.f;
+        kh[r] = ok ? elu1(kk[mb][r] + bk[mb][r]) : 0.f;
+        vh[r] = ok ? vv[mb][r] + bv[mb][r] : 0.f;
       }
 #pragma unroll
       for (int m = 0; m < 4; ++m)
@@ -374,9 +272,9 @@ __global__ __launch_bounds__(256) void fmt_kv_partial_kernel(const float* __rest
     for (int mb = 0; mb < 2; ++mb) {
       const int h = 4 * mb + g;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) red[wv][h * 16 + i] = kv[mb][i];
+      for (int i = 0; i < 16; ++i) red[wv][kv_at(h, i >> 2, i & 3)] = kv[mb][i];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) red[wv][128 + h * 4 + i] = ks[mb][i];
+      for (int i = 0; i < 4; ++i) red[wv][ksum_at(h, i)] = ks[mb][i];
     }
   }
   __syncthreads();
@@ -407,11 +305,10 @@ __global__ __launch_bounds__(1024) void fmt_kv_combine_kernel(const float* __res
   }
 }
 
-// The rest of EncoderLayer.forward for tiles of 16 query tokens, entirely in registers;
-// kApplyNT tiles are processed together so their MFMA chains interleave.
-constexpr int kApplyNT = 1;
+// The rest of EncoderLayer.forward for tiles of 16 query tokens, entirely in registers.
 // (amdgpu_waves_per_eu(5) fits it in 94 VGPRs without AGPRs, 5 waves/SIMD instead of 4: the 8 applies
-// measured 456.6 vs 448.1 us per step, 6 waves (80 VGPRs + scratch) 472.0 -- profiles/r11n: not kept)
+// measured 456.6 vs 448.1 us per step, 6 waves (80 VGPRs + scratch) 472.0 -- profiles/r11n: not kept.
+// Two tiles per call of the tile lambda, their MFMA chains interleaved, was an option nobody selected.)
 __global__ __launch_bounds__(256) void fmt_apply_kernel(float* __restrict__ x, int L, const float* __restrict__ kvg,
                                                         long kv_stride, const float* __restrict__ w, int tpw) {
   __shared__ __attribute__((aligned(16))) float kvs[kKV];
@@ -421,9 +318,7 @@ __global__ __launch_bounds__(256) void fmt_apply_kernel(float* __restrict__ x, i
   constexpr int kVB2 = 128, kVLN = 160;
   __shared__ __attribute__((aligned(16))) float vec[288];
   const int v = blockIdx.y;
-  // wave index wave-uniform (readfirstlane): the tile loop is then scalar control flow, not a divergent
-  // loop whose per-lane exits make the compiler wait vmcnt(0) (stores included) at its head
-  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, wv = wave_index();
   const int g = lane >> 4;
   if (threadIdx.x < kKV) kvs[threadIdx.x] = kvg[(size_t)v * kv_stride + threadIdx.x];
   for (int i = threadIdx.x; i < 288; i += blockDim.x)
@@ -436,118 +331,86 @@ __global__ __launch_bounds__(256) void fmt_apply_kernel(float* __restrict__ x, i
   stage_afrag<32, 64, true>(w + TMVS_ENC_W2T, frag + 4096);
   __syncthreads();
   float* xv = x + (size_t)v * L * kD;
-  const int tile0 = (blockIdx.x * 4 + wv) * tpw;
-  constexpr int NT = kApplyNT;
+  const int tile0 = first_tile(wv, tpw);
   // two token buffers used alternately (the loop unrolled by two, so they swap by name: a
   // loop-carried copy made the compiler wait vmcnt(0) -- this tile's stores included -- at the latch)
-  floatx4 xa[NT][2], xb[NT][2];
-#pragma unroll
-  for (int p = 0; p < NT; ++p) {
-    const int t = (tile0 + p) * 16 + (lane & 15);
-    if (p < tpw) load_token_frag(xv + (size_t)(t < L ? t : L - 1) * kD, xa[p], lane);
-  }
-  auto tile = [&](int it, floatx4 (&cur)[NT][2], floatx4 (&nxt)[NT][2]) {
-    int salt = 0;  // opaque offset: fragment reads stay in the loop (not hoisted back into VGPRs)
-    asm volatile("" : "+s"(salt));  // an SGPR: a VGPR here could alias a pending load (vmcnt wait)
+  floatx4_t xa[2], xb[2];
+  load_token_frag(row(xv, tile0 * 16 + (lane & 15), L), xa, lane);
+  auto tile = [&](int it, floatx4_t (&cur)[2], floatx4_t (&nxt)[2]) {
+    const int salt = opaque_zero();
     const float* fr = frag + salt;
     const float* vb = vec + salt;
-    float* row[NT];
-    bool ok[NT];
-    floatx4 xs[NT][2];
+    const int t = (tile0 + it) * 16 + (lane & 15);
+    const bool ok = t < L;
+    float* out = row(xv, t, L);
+    floatx4_t xs[2] = {cur[0], cur[1]};
+    load_token_frag(row(xv, t + 16, L), nxt, lane);
+    floatx4_t q[2], msg[2];
+    mfma_linear_lds<32, 32>(fr, xs, q, lane);
 #pragma unroll
-    for (int p = 0; p < NT; ++p) {
-      const int t = (tile0 + it + p) * 16 + (lane & 15);
-      ok[p] = t < L && it + p < tpw;
-      row[p] = xv + (size_t)(t < L ? t : L - 1) * kD;
-      xs[p][0] = cur[p][0];
-      xs[p][1] = cur[p][1];
-      const int tn = t + 16 * NT;
-      // unconditional (clamped row; a prefetch past the wave's range is never used): a branch here made
-      // the compiler wait vmcnt(0) for this prefetch before the tile's first MFMA
-      load_token_frag(xv + (size_t)(tn < L ? tn : L - 1) * kD, nxt[p], lane);
-    }
-    floatx4 q[NT][2], msg[NT][2];
-    mfma_linear_lds<32, 32, NT>(fr, xs, q, lane);
+    for (int mb = 0; mb < 2; ++mb) {
+      const int h = 4 * mb + g;
+      // head h's K/V summary, bias and Ksum as 16-byte LDS reads issued together
+      float bq[4], ksum[4], kvm[4][4];
+      ld4(vb + 4 * h, bq);
+      ld4(kvs + ksum_at(h, 0), ksum);
 #pragma unroll
-    for (int p = 0; p < NT; ++p)
+      for (int m = 0; m < 4; ++m) ld4(kvs + kv_at(h, m, 0), kvm[m]);
+      float qe[4];
 #pragma unroll
-      for (int mb = 0; mb < 2; ++mb) {
-        const int h = 4 * mb + g;
-        // head h's K/V summary, bias and Ksum as 16-byte LDS reads issued together
-        const float4 bq = *reinterpret_cast<const float4*>(vb + 4 * h);
-        const float4 ks4 = *reinterpret_cast<const float4*>(kvs + 128 + h * 4);
-        float4 kv4[4];
+      for (int d = 0; d < 4; ++d) qe[d] = elu1(q[mb][d] + bq[d]);
+      float den = 0.f;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) kv4[m] = *reinterpret_cast<const float4*>(kvs + h * 16 + m * 4);
-        const float bqa[4] = {bq.x, bq.y, bq.z, bq.w}, ksa[4] = {ks4.x, ks4.y, ks4.z, ks4.w};
-        float qe[4];
+      for (int d = 0; d < 4; ++d) den = fmaf(qe[d], ksum[d], den);
+      const float z = 1.f / (den + kAttnEps);
 #pragma unroll
-        for (int d = 0; d < 4; ++d) qe[d] = elu1(q[p][mb][d] + bqa[d]);
-        float den = 0.f;
+      for (int m = 0; m < 4; ++m) {
+        float num = 0.f;
 #pragma unroll
-        for (int d = 0; d < 4; ++d) den = fmaf(qe[d], ksa[d], den);
-        const float z = 1.f / (den + 1e-6f);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const float kva[4] = {kv4[m].x, kv4[m].y, kv4[m].z, kv4[m].w};
-          float num = 0.f;
-#pragma unroll
-          for (int d = 0; d < 4; ++d) num = fmaf(qe[d], kva[d], num);
-          msg[p][mb][m] = num * z;
-        }
+        for (int d = 0; d < 4; ++d) num = fmaf(qe[d], kvm[m][d], num);
+        msg[mb][m] = num * z;
       }
-    floatx4 a[NT][2];
-    mfma_linear_lds<32, 32, NT>(fr + 1024, msg, a, lane);
+    }
+    floatx4_t a[2];
+    mfma_linear_lds<32, 32>(fr + 1024, msg, a, lane);
 #pragma unroll
-    for (int p = 0; p < NT; ++p) {
+    for (int mb = 0; mb < 2; ++mb) {
+      float bo[4];
+      ld4(vb + 32 + 16 * mb + 4 * g, bo);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) xs[mb][r] = xs[mb][r] + (a[mb][r] + bo[r]);
+    }
+    layer_norm_frag(xs, vb + kVLN, vb + kVLN + kD, lane);
+    floatx4_t hdn[4], ff[2];
+    mfma_linear_lds<64, 32>(fr + 2048, xs, hdn, lane);
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) {
+      float b1[4];
+      ld4(vb + 64 + 16 * mb + 4 * g, b1);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) hdn[mb][r] = relu(hdn[mb][r] + b1[r]);
+    }
+    mfma_linear_lds<32, 64>(fr + 4096, hdn, ff, lane);
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+      float b2[4];
+      ld4(vb + kVB2 + 16 * mb + 4 * g, b2);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) xs[mb][r] = xs[mb][r] + (ff[mb][r] + b2[r]);
+    }
+    layer_norm_frag(xs, vb + kVLN + 2 * kD, vb + kVLN + 3 * kD, lane);
+    if (ok) {
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb)
-      {
-        const float4 b4 = *reinterpret_cast<const float4*>(vb + 32 + 16 * mb + 4 * g);
-        const float bo[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) xs[p][mb][r] = xs[p][mb][r] + (a[p][mb][r] + bo[r]);
-      }
-      layer_norm_frag(xs[p], vb + kVLN, vb + kVLN + kD, lane);
-    }
-    floatx4 hdn[NT][4], ff[NT][2];
-    mfma_linear_lds<64, 32, NT>(fr + 2048, xs, hdn, lane);
-#pragma unroll
-    for (int p = 0; p < NT; ++p)
-#pragma unroll
-      for (int mb = 0; mb < 4; ++mb)
-      {
-        const float4 b4 = *reinterpret_cast<const float4*>(vb + 64 + 16 * mb + 4 * g);
-        const float b1[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) hdn[p][mb][r] = relu(hdn[p][mb][r] + b1[r]);
-      }
-    mfma_linear_lds<32, 64, NT>(fr + 4096, hdn, ff, lane);
-#pragma unroll
-    for (int p = 0; p < NT; ++p) {
-#pragma unroll
-      for (int mb = 0; mb < 2; ++mb)
-      {
-        const float4 b4 = *reinterpret_cast<const float4*>(vb + kVB2 + 16 * mb + 4 * g);
-        const float b2[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) xs[p][mb][r] = xs[p][mb][r] + (ff[p][mb][r] + b2[r]);
-      }
-      layer_norm_frag(xs[p], vb + kVLN + 2 * kD, vb + kVLN + 3 * kD, lane);
-      if (ok[p]) {
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-          *reinterpret_cast<float4*>(row[p] + 16 * mb + 4 * g) =
-              make_float4(xs[p][mb][0], xs[p][mb][1], xs[p][mb][2], xs[p][mb][3]);
-      }
+        *reinterpret_cast<float4*>(out + 16 * mb + 4 * g) = make_float4(xs[mb][0], xs[mb][1], xs[mb][2], xs[mb][3]);
     }
   };
 #pragma unroll 1
-  for (int it = 0; it < tpw; it += 2 * NT) {
+  for (int it = 0; it < tpw; it += 2) {
     if ((tile0 + it) * 16 >= L) break;  // wave-uniform
     tile(it, xa, xb);
-    if (it + NT >= tpw || (tile0 + it + NT) * 16 >= L) break;
-    tile(it + NT, xb, xa);
+    if (it + 1 >= tpw || (tile0 + it + 1) * 16 >= L) break;
+    tile(it + 1, xb, xa);
   }
 }
 
@@ -587,8 +450,7 @@ static int kv_nblk(int nv, int S) {
 // waves/SIMD on average, r05f).
 static int apply_tiles_per_wave(int nv, int L) {
   const long tiles = (long)nv * ((L + 15) / 16);
-  const long tpw = std::max<long>(1, (tiles + wave_slots_apply() - 1) / wave_slots_apply());
-  return (int)((tpw + kApplyNT - 1) / kApplyNT * kApplyNT);  // whole groups of kApplyNT tiles
+  return (int)std::max<long>(1, (tiles + wave_slots_apply() - 1) / wave_slots_apply());
 }
 static int apply_nblk(int L, int tpw) { return (L + 16 * 4 * tpw - 1) / (16 * 4 * tpw); }
 
@@ -622,7 +484,7 @@ extern "C" int tmvs_fmt_kv_grouped(const float* source, int nv, int group_nv, in
   if (workspace_bytes < tmvs_fmt_kv_grouped_workspace(nv, group_nv, s_tokens)) return TMVS_ERR_ARG;
   const int nblk = kv_nblk(group_nv, s_tokens);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(fmt_kv_partial_kernel, dim3(nblk, nv), dim3(kKvBlock), 0, st, source, s_tokens, enc_w,
+  hipLaunchKernelGGL(fmt_kv_partial_kernel, dim3(nblk, nv), dim3(256), 0, st, source, s_tokens, enc_w,
                      (float*)workspace, kv_tiles_per_wave(group_nv, s_tokens));
   TMVS_CHECK_LAUNCH();
   hipLaunchKernelGGL(fmt_kv_combine_kernel, dim3(nv, kKV / 32), dim3(1024), 0, st, (const float*)workspace, nblk, kv);
@@ -639,8 +501,7 @@ extern "C" int tmvs_fmt_kv(const float* source, int nv, int s_tokens, const floa
 extern "C" int tmvs_fmt_apply_tiled(float* x, int nv, int l_tokens, const float* kv, long kv_view_stride,
                                     const float* enc_w, int tiles_per_wave, void* stream) {
   if (!x || !kv || !enc_w || nv <= 0 || l_tokens <= 0 || kv_view_stride < 0) return TMVS_ERR_ARG;
-  const int tpw = tiles_per_wave > 0 ? (tiles_per_wave + kApplyNT - 1) / kApplyNT * kApplyNT
-                                     : apply_tiles_per_wave(nv, l_tokens);
+  const int tpw = tiles_per_wave > 0 ? tiles_per_wave : apply_tiles_per_wave(nv, l_tokens);
   hipLaunchKernelGGL(fmt_apply_kernel, dim3(apply_nblk(l_tokens, tpw), nv), dim3(256), 0, (hipStream_t)stream, x,
                      l_tokens, kv, kv_view_stride, enc_w, tpw);
   TMVS_CHECK_LAUNCH();

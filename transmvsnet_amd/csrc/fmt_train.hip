@@ -9,18 +9,14 @@
 //   tmvs_linattn_bwd_q     dq (through the elu), and dKV / dKsum reduced over the queries of each
 //                          K/V group (per view for self layers, all views for cross layers)
 //   tmvs_linattn_bwd_kv    dk (through the elu), dv of the source tokens
-// KV layout as the forward (csrc/fmt.hip): kv[h*16 + m*4 + d] = sum_s K[s,h,d] V[s,h,m], Ksum at
-// 128 + h*4 + d. fp32 per token, fp64 in every cross-token reduction, no atomics.
+// KV layout, elu feature map and epsilons as the forward (fmt_common.h). fp32 per token, fp64 in every
+// cross-token reduction, no atomics.
+#include "fmt_common.h"
 #include "train_reduce.h"
 
 namespace tmvs {
 
 constexpr int kTB = 256;
-constexpr float kLnEps = 1e-5f;
-constexpr float kAttnEps = 1e-6f;
-
-__device__ __forceinline__ float elu1f(float x) { return (x > 0.f ? x : expm1f(x)) + 1.f; }
-__device__ __forceinline__ float elu1_grad(float x) { return x > 0.f ? 1.f : expf(x); }
 
 // y[t][o] = sum_i W[o][i] x[t][i] + b[o] for a torch Linear weight W [OUT][IN]; TRANS: y[t][o] = sum_i W[i][o] x[t][i]
 // for W [IN][OUT] (the data gradient dx = dy W of a Linear with weight W); relu_of masks y where relu_of <= 0;
@@ -310,8 +306,6 @@ __global__ __launch_bounds__(kTB) void layer_norm_bwd_kernel(const float* __rest
 // is one contiguous 1 KiB span (the former token-per-thread loop over heads read 128-B-strided quads).
 constexpr int kTokPerBlock = kTB / 8;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 // msg[t][h*4+m] = (sum_d Q[h,d] KV[h][m][d]) / (sum_d Q[h,d] Ks[h][d] + eps); tokens of group gi use kv[gi*kvs]
 __global__ __launch_bounds__(kTB) void linattn_fwd_kernel(const float* __restrict__ q, long T, long tpg,
                                                           const float* __restrict__ kv, long kv_stride,
@@ -321,17 +315,17 @@ __global__ __launch_bounds__(kTB) void linattn_fwd_kernel(const float* __restric
   if (t >= T) return;
   const float* K = kv + (t / tpg) * kv_stride;
   const float4 q4 = ld4(q + t * 32 + h * 4);
-  const float Q[4] = {elu1f(q4.x), elu1f(q4.y), elu1f(q4.z), elu1f(q4.w)};
+  const float Q[4] = {elu1(q4.x), elu1(q4.y), elu1(q4.z), elu1(q4.w)};
   float den = 0.f;
 #pragma unroll
-  for (int d = 0; d < 4; ++d) den = fmaf(Q[d], K[128 + h * 4 + d], den);
+  for (int d = 0; d < 4; ++d) den = fmaf(Q[d], K[ksum_at(h, d)], den);
   const float z = 1.f / (den + kAttnEps);
   float o[4];
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     float num = 0.f;
 #pragma unroll
-    for (int d = 0; d < 4; ++d) num = fmaf(Q[d], K[h * 16 + m * 4 + d], num);
+    for (int d = 0; d < 4; ++d) num = fmaf(Q[d], K[kv_at(h, m, d)], num);
     o[m] = num * z;
   }
   *reinterpret_cast<float4*>(msg + t * 32 + h * 4) = make_float4(o[0], o[1], o[2], o[3]);
@@ -344,16 +338,16 @@ __global__ __launch_bounds__(kTB) void linattn_bwd_q_kernel(const float* __restr
                                                             long T, long tpg, long tpb, const float* __restrict__ kv,
                                                             long kv_stride, float* __restrict__ dq,
                                                             double* __restrict__ partial) {
-  __shared__ double red[kTB / 64][160];
+  __shared__ double red[kTB / 64][kKV];
   const long t0 = (long)blockIdx.x * tpb, t1 = t0 + tpb < T ? t0 + tpb : T;
   const float* K = kv + (t0 / tpg) * kv_stride;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int h = threadIdx.x & 7;
   float kvh[16], ksh[4];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) kvh[i] = K[h * 16 + i];
+  for (int i = 0; i < 16; ++i) kvh[i] = K[kv_at(h, i >> 2, i & 3)];
 #pragma unroll
-  for (int d = 0; d < 4; ++d) ksh[d] = K[128 + h * 4 + d];
+  for (int d = 0; d < 4; ++d) ksh[d] = K[ksum_at(h, d)];
   float acc[20];
 #pragma unroll
   for (int i = 0; i < 20; ++i) acc[i] = 0.f;
@@ -362,7 +356,7 @@ __global__ __launch_bounds__(kTB) void linattn_bwd_q_kernel(const float* __restr
     const float qr[4] = {q4.x, q4.y, q4.z, q4.w}, dm[4] = {d4.x, d4.y, d4.z, d4.w};
     float Q[4];
 #pragma unroll
-    for (int d = 0; d < 4; ++d) Q[d] = elu1f(qr[d]);
+    for (int d = 0; d < 4; ++d) Q[d] = elu1(qr[d]);
     float den = 0.f;
 #pragma unroll
     for (int d = 0; d < 4; ++d) den = fmaf(Q[d], ksh[d], den);
@@ -397,12 +391,12 @@ __global__ __launch_bounds__(kTB) void linattn_bwd_q_kernel(const float* __restr
     val += __shfl_xor(val, 8, 64);
     val += __shfl_xor(val, 16, 64);
     val += __shfl_xor(val, 32, 64);
-    if (lane < 8) red[wv][i < 16 ? h * 16 + i : 128 + h * 4 + (i - 16)] = val;
+    if (lane < 8) red[wv][i < 16 ? kv_at(h, i >> 2, i & 3) : ksum_at(h, i - 16)] = val;
   }
   __syncthreads();
-  if (threadIdx.x < 160) {
+  if (threadIdx.x < kKV) {
     const int i = threadIdx.x;
-    partial[(size_t)blockIdx.x * 160 + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    partial[(size_t)blockIdx.x * kKV + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
   }
 }
 
@@ -411,15 +405,15 @@ __global__ __launch_bounds__(kTB) void linattn_bwd_q_kernel(const float* __restr
 __global__ void linattn_group_combine_kernel(const double* __restrict__ partial, int blocks_per_group,
                                              float* __restrict__ dkv) {
   const int g = blockIdx.x, i = threadIdx.x;
-  if (i >= 160) return;
-  const double* p = partial + (size_t)g * blocks_per_group * 160 + i;
+  if (i >= kKV) return;
+  const double* p = partial + (size_t)g * blocks_per_group * kKV + i;
   double c[4] = {0.0, 0.0, 0.0, 0.0};
   int j = 0;
   for (; j + 4 <= blocks_per_group; j += 4)
 #pragma unroll
-    for (int u = 0; u < 4; ++u) c[u] += p[(size_t)(j + u) * 160];
-  for (; j < blocks_per_group; ++j) c[j & 3] += p[(size_t)j * 160];
-  dkv[(size_t)g * 160 + i] = (float)((c[0] + c[1]) + (c[2] + c[3]));
+    for (int u = 0; u < 4; ++u) c[u] += p[(size_t)(j + u) * kKV];
+  for (; j < blocks_per_group; ++j) c[j & 3] += p[(size_t)j * kKV];
+  dkv[(size_t)g * kKV + i] = (float)((c[0] + c[1]) + (c[2] + c[3]));
 }
 
 // source side: dK[s,h,d] = sum_m dKV[h][m][d] V[s,h,m] + dKs[h][d]; dV[s,h,m] = sum_d dKV[h][m][d] K[s,h,d]
@@ -429,24 +423,24 @@ __global__ __launch_bounds__(kTB) void linattn_bwd_kv_kernel(const float* __rest
   const int h = threadIdx.x & 7;
   const long s = (long)blockIdx.x * kTokPerBlock + (threadIdx.x >> 3);
   if (s >= S) return;
-  const float* G = dkv + (s / spg) * 160;
+  const float* G = dkv + (s / spg) * kKV;
   const float4 k4 = ld4(k + s * 32 + h * 4), v4 = ld4(v + s * 32 + h * 4);
   const float kr[4] = {k4.x, k4.y, k4.z, k4.w}, V[4] = {v4.x, v4.y, v4.z, v4.w};
   float Kf[4], ok[4], ov[4];
 #pragma unroll
-  for (int d = 0; d < 4; ++d) Kf[d] = elu1f(kr[d]);
+  for (int d = 0; d < 4; ++d) Kf[d] = elu1(kr[d]);
 #pragma unroll
   for (int d = 0; d < 4; ++d) {
-    float g = G[128 + h * 4 + d];
+    float g = G[ksum_at(h, d)];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) g = fmaf(G[h * 16 + m * 4 + d], V[m], g);
+    for (int m = 0; m < 4; ++m) g = fmaf(G[kv_at(h, m, d)], V[m], g);
     ok[d] = g * elu1_grad(kr[d]);
   }
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     float g = 0.f;
 #pragma unroll
-    for (int d = 0; d < 4; ++d) g = fmaf(G[h * 16 + m * 4 + d], Kf[d], g);
+    for (int d = 0; d < 4; ++d) g = fmaf(G[kv_at(h, m, d)], Kf[d], g);
     ov[m] = g;
   }
   *reinterpret_cast<float4*>(dk + s * 32 + h * 4) = make_float4(ok[0], ok[1], ok[2], ok[3]);
@@ -571,7 +565,7 @@ static long group_chunk(long tpg) {
 }
 
 extern "C" size_t tmvs_linattn_bwd_workspace(long tokens, long tokens_per_group) {
-  return (size_t)(tokens / group_chunk(tokens_per_group)) * 160 * sizeof(double);
+  return (size_t)(tokens / group_chunk(tokens_per_group)) * kKV * sizeof(double);
 }
 
 extern "C" int tmvs_linattn_bwd_q(const float* q, const float* dmsg, long tokens, long tokens_per_group,

@@ -13,26 +13,6 @@
 
 namespace tmvs {
 
-struct LinAxis {
-  int i0, i1;
-  float l0, l1;
-};
-
-// area_pixel_compute_source_index + guard_index_and_lambda (align_corners=False, linear)
-__device__ __forceinline__ LinAxis lin_axis(int dst, int in_size, int out_size) {
-  const float scale = (float)in_size / (float)out_size;
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  LinAxis a;
-  a.i0 = min((int)floorf(src), in_size - 1);
-  a.i1 = a.i0 + (a.i0 < in_size - 1 ? 1 : 0);
-  float l = src - (float)a.i0;
-  l = fminf(fmaxf(l, 0.f), 1.f);
-  a.l1 = l;
-  a.l0 = 1.f - l;
-  return a;
-}
-
 __device__ __forceinline__ float upsample_at(const float* __restrict__ prev, int ph, int pw, int y, int x, int H,
                                              int W) {
   const LinAxis ay = lin_axis(y, ph, H);

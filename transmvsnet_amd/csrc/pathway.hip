@@ -14,84 +14,35 @@ constexpr int kTile = 16;
 constexpr int kHalo = kTile + 2;
 constexpr int kCoarse = kTile / 2 + 2;
 
-struct Axis {
-  int i0, i1;
-  float l0, l1;
-};
-
-// The lateral halo values (NCHW, the FeatureNet output) do not depend on the coarse reduction:
-// every thread requests its <= 2 halo pixels' CF channels before phase 1, so their HBM latency
-// overlaps the reduction instead of sitting after the first barrier. Out-of-image pixels read 0.
-constexpr int kHaloIters = (kHalo * kHalo + 255) / 256;
+// The two kernels below share the tile decode, the lateral prefetch and phase 1. A tile is kTile wide and TH
+// high (16 for the 16-channel kernel, 16R for the rows kernel); its halo is HH = TH + 2 rows of kHalo, its coarse
+// patch CH = TH / 2 + 2 rows of kCoarse. Phase 2 (bilinear x2 + lateral into the halo) is spelled out in each
+// kernel: as a shared function with a store functor it cost the 16-channel kernel 12 VGPRs and a wave per SIMD
+// (profiles/fmt_pathway_scaffold_resources.md).
+constexpr int halo_iters(int HH) { return (HH * kHalo + 255) / 256; }  // halo pixels per thread
 
 // Tiles are dealt out XCD-contiguously over a 1-D grid (x fastest, then y, then view): consecutive
 // block ids go to different XCDs, so with the plain 3-D grid a tile's x/y neighbours -- which read
 // the same 128-B lines of the halo rows (an 18-float NCHW row spans 2-3 lines) -- sat behind
 // different L2s and each re-fetched them.
+template <int TH>
 __device__ __forceinline__ void pathway_tile(int W, int H, int& v, int& y0, int& x0) {
-  const int nbx = (W + kTile - 1) / kTile, nby = (H + kTile - 1) / kTile;
+  const int nbx = (W + kTile - 1) / kTile, nby = (H + TH - 1) / TH;
   int lb = xcd_remap(blockIdx.x, gridDim.x);
   x0 = (lb % nbx) * kTile;
   lb /= nbx;
-  y0 = (lb % nby) * kTile;
+  y0 = (lb % nby) * TH;
   v = lb / nby;
 }
 
-template <int CF>
+// The lateral halo values (NCHW, the FeatureNet output) do not depend on the coarse reduction:
+// every thread requests its halo pixels' CF channels before phase 1, so their HBM latency
+// overlaps the reduction instead of sitting after the first barrier. Out-of-image pixels read 0.
+template <int CF, int HH>
 __device__ __forceinline__ void load_lateral(const float* __restrict__ lv, int y0, int x0, int H, int W,
-                                             float (&lat)[kHaloIters][CF]) {
+                                             float (&lat)[halo_iters(HH)][CF]) {
 #pragma unroll
-  for (int it = 0; it < kHaloIters; ++it) {
-    const int idx = threadIdx.x + 256 * it;
-    const int r = idx / kHalo, c = idx - r * kHalo;
-    const int y = y0 - 1 + r, x = x0 - 1 + c;
-    const bool ok = idx < kHalo * kHalo && y >= 0 && y < H && x >= 0 && x < W;
-#pragma unroll
-    for (int o = 0; o < CF; ++o) lat[it][o] = ok ? lv[((size_t)o * H + y) * W + x] : 0.f;
-  }
-}
-
-__device__ __forceinline__ Axis up_axis(int dst, int in_size, int out_size) {
-  const float scale = (float)in_size / (float)out_size;
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  Axis a;
-  a.i0 = min((int)floorf(src), in_size - 1);
-  a.i1 = a.i0 + (a.i0 < in_size - 1 ? 1 : 0);
-  const float l = fminf(fmaxf(src - (float)a.i0, 0.f), 1.f);
-  a.l1 = l;
-  a.l0 = 1.f - l;
-  return a;
-}
-
-// Stage-3 form with R output rows per thread: a workgroup owns a 16 x 16R tile, so the two
-// barriers, the coarse/halo staging and every scalar weight load are shared by R pixels. Tap
-// (i, k) feeds the R accumulator sets back to back; each output's chain runs in (i, k, o) order
-// whatever R is, so the results do not depend on it.
-constexpr int kPathwayRows = 2;
-template <int CC, int CF, int R>
-__global__ __launch_bounds__(256) void pathway_rows_kernel(const float* __restrict__ coarse,
-                                                           const float* __restrict__ lateral, long lat_stride,
-                                                           const float* __restrict__ wred,
-                                                           const float* __restrict__ wsm, int h, int w,
-                                                           float* __restrict__ out) {
-  constexpr int TH = kTile * R, HH = TH + 2, CH = TH / 2 + 2;
-  constexpr int NIT = (HH * kHalo + 255) / 256;
-  __shared__ float red[CF][CH][kCoarse + 1];
-  __shared__ float inb[CF][HH][kHalo + 1];
-  const int H = 2 * h, W = 2 * w;
-  const int nbx = (W + kTile - 1) / kTile, nby = (H + TH - 1) / TH;
-  int lb = xcd_remap(blockIdx.x, gridDim.x);
-  const int x0 = (lb % nbx) * kTile;
-  lb /= nbx;
-  const int y0 = (lb % nby) * TH;
-  const int v = lb / nby;
-  const int cy0 = y0 / 2 - 1, cx0 = x0 / 2 - 1;
-  const float* cv = coarse + (size_t)v * h * w * CC;
-  const float* lv = lateral + (size_t)v * lat_stride;
-  float lat[NIT][CF];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
+  for (int it = 0; it < halo_iters(HH); ++it) {
     const int idx = threadIdx.x + 256 * it;
     const int r = idx / kHalo, c = idx - r * kHalo;
     const int y = y0 - 1 + r, x = x0 - 1 + c;
@@ -99,7 +50,13 @@ __global__ __launch_bounds__(256) void pathway_rows_kernel(const float* __restri
 #pragma unroll
     for (int o = 0; o < CF; ++o) lat[it][o] = ok ? lv[((size_t)o * H + y) * W + x] : 0.f;
   }
-  // 1) 1x1 reduction of the coarse patch
+}
+
+// Phase 1: the 1x1 reduction of the CH x kCoarse coarse patch at (cy0, cx0) into LDS (pixels outside the
+// coarse map are left unwritten: phase 2 never reads them)
+template <int CC, int CF, int CH>
+__device__ __forceinline__ void reduce_coarse(const float* __restrict__ cv, const float* __restrict__ wred, int cy0,
+                                              int cx0, int h, int w, float (&red)[CF][CH][kCoarse + 1]) {
   for (int idx = threadIdx.x; idx < CH * kCoarse; idx += 256) {
     const int r = idx / kCoarse, c = idx - r * kCoarse;
     const int cy = cy0 + r, cx = cx0 + c;
@@ -124,10 +81,33 @@ __global__ __launch_bounds__(256) void pathway_rows_kernel(const float* __restri
 #pragma unroll
     for (int o = 0; o < CF; ++o) red[o][r][c] = acc[o];
   }
+}
+
+// Stage-3 form with R output rows per thread: a workgroup owns a 16 x 16R tile, so the two
+// barriers, the coarse/halo staging and every scalar weight load are shared by R pixels. Tap
+// (i, k) feeds the R accumulator sets back to back; each output's chain runs in (i, k, o) order
+// whatever R is, so the results do not depend on it.
+constexpr int kPathwayRows = 2;
+template <int CC, int CF, int R>
+__global__ __launch_bounds__(256) void pathway_rows_kernel(const float* __restrict__ coarse,
+                                                           const float* __restrict__ lateral, long lat_stride,
+                                                           const float* __restrict__ wred,
+                                                           const float* __restrict__ wsm, int h, int w,
+                                                           float* __restrict__ out) {
+  constexpr int TH = kTile * R, HH = TH + 2, CH = TH / 2 + 2;
+  __shared__ float red[CF][CH][kCoarse + 1];
+  __shared__ float inb[CF][HH][kHalo + 1];
+  const int H = 2 * h, W = 2 * w;
+  int v, y0, x0;
+  pathway_tile<TH>(W, H, v, y0, x0);
+  const int cy0 = y0 / 2 - 1, cx0 = x0 / 2 - 1;
+  float lat[halo_iters(HH)][CF];
+  load_lateral<CF, HH>(lateral + (size_t)v * lat_stride, y0, x0, H, W, lat);
+  reduce_coarse<CC, CF, CH>(coarse + (size_t)v * h * w * CC, wred, cy0, cx0, h, w, red);  // 1)
   __syncthreads();
   // 2) bilinear x2 up-sampling + lateral over the (16R+2) x 18 halo (zero outside the image)
 #pragma unroll
-  for (int it = 0; it < NIT; ++it) {
+  for (int it = 0; it < halo_iters(HH); ++it) {
     const int idx = threadIdx.x + 256 * it;
     if (idx >= HH * kHalo) break;
     const int r = idx / kHalo, c = idx - r * kHalo;
@@ -137,7 +117,7 @@ __global__ __launch_bounds__(256) void pathway_rows_kernel(const float* __restri
       for (int o = 0; o < CF; ++o) inb[o][r][c] = 0.f;
       continue;
     }
-    const Axis ay = up_axis(y, h, H), ax = up_axis(x, w, W);
+    const LinAxis ay = lin_axis(y, h, H), ax = lin_axis(x, w, W);
     const int r0 = ay.i0 - cy0, r1 = ay.i1 - cy0, c0 = ax.i0 - cx0, c1 = ax.i1 - cx0;
 #pragma unroll
     for (int o = 0; o < CF; ++o) {
@@ -187,8 +167,6 @@ __global__ __launch_bounds__(256) void pathway_rows_kernel(const float* __restri
 // VGPRs. The halo is stored [pixel][16 ch] with channels interleaved so a lane's 4 k-values
 // (channels kgrp, 4+kgrp, 8+kgrp, 12+kgrp) are one ds_read_b128, quad-swizzled by pixel
 // (bank-conflict free for 16 consecutive pixels, as in costreg.hip).
-typedef float floatx4_p __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ int halo16_index(int vox, int o) {
   const int q = (o & 3) ^ ((vox >> 1) & 3);
   return vox * 16 + q * 4 + (o >> 2);
@@ -205,37 +183,11 @@ __global__ __launch_bounds__(256) void pathway16_mfma_kernel(const float* __rest
   __shared__ __attribute__((aligned(16))) float inb[kHalo * kHalo * CF];
   const int H = 2 * h, W = 2 * w;
   int v, y0, x0;
-  pathway_tile(W, H, v, y0, x0);
+  pathway_tile<kTile>(W, H, v, y0, x0);
   const int cy0 = y0 / 2 - 1, cx0 = x0 / 2 - 1;
-  const float* cv = coarse + (size_t)v * h * w * CC;
-  const float* lv = lateral + (size_t)v * lat_stride;
-  float lat[kHaloIters][CF];
-  load_lateral<CF>(lv, y0, x0, H, W, lat);
-  // 1) 1x1 reduction of the coarse patch (as pathway_rows_kernel)
-  for (int idx = threadIdx.x; idx < kCoarse * kCoarse; idx += blockDim.x) {
-    const int r = idx / kCoarse, c = idx - r * kCoarse;
-    const int cy = cy0 + r, cx = cx0 + c;
-    if (cy < 0 || cy >= h || cx < 0 || cx >= w) continue;
-    float xin[CC];
-    const float* p = cv + ((size_t)cy * w + cx) * CC;
-#pragma unroll
-    for (int i4 = 0; i4 < CC / 4; ++i4) {
-      const float4 t = *reinterpret_cast<const float4*>(p + 4 * i4);
-      xin[4 * i4] = t.x;
-      xin[4 * i4 + 1] = t.y;
-      xin[4 * i4 + 2] = t.z;
-      xin[4 * i4 + 3] = t.w;
-    }
-    float acc[CF];
-#pragma unroll
-    for (int o = 0; o < CF; ++o) acc[o] = 0.f;
-#pragma unroll 2
-    for (int i = 0; i < CC; ++i)
-#pragma unroll
-      for (int o = 0; o < CF; ++o) acc[o] = fmaf(wred[i * CF + o], xin[i], acc[o]);
-#pragma unroll
-    for (int o = 0; o < CF; ++o) red[o][r][c] = acc[o];
-  }
+  float lat[halo_iters(kHalo)][CF];
+  load_lateral<CF, kHalo>(lateral + (size_t)v * lat_stride, y0, x0, H, W, lat);
+  reduce_coarse<CC, CF, kCoarse>(coarse + (size_t)v * h * w * CC, wred, cy0, cx0, h, w, red);  // 1)
   // A fragments meanwhile: lane (co = col, kgrp), tap t, k-step j -> W[co][ci = 4j + kgrp][t]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int col = lane & 15, kgrp = lane >> 4;
@@ -247,7 +199,7 @@ __global__ __launch_bounds__(256) void pathway16_mfma_kernel(const float* __rest
   __syncthreads();
   // 2) bilinear x2 up-sampling + lateral over the 18x18 halo (zero outside the image)
 #pragma unroll
-  for (int it = 0; it < kHaloIters; ++it) {
+  for (int it = 0; it < halo_iters(kHalo); ++it) {
     const int idx = threadIdx.x + 256 * it;
     if (idx >= kHalo * kHalo) break;
     const int r = idx / kHalo, c = idx - r * kHalo;
@@ -257,7 +209,7 @@ __global__ __launch_bounds__(256) void pathway16_mfma_kernel(const float* __rest
       for (int o = 0; o < CF; ++o) inb[halo16_index(idx, o)] = 0.f;
       continue;
     }
-    const Axis ay = up_axis(y, h, H), ax = up_axis(x, w, W);
+    const LinAxis ay = lin_axis(y, h, H), ax = lin_axis(x, w, W);
     const int r0 = ay.i0 - cy0, r1 = ay.i1 - cy0, c0 = ax.i0 - cx0, c1 = ax.i1 - cx0;
 #pragma unroll
     for (int o = 0; o < CF; ++o) {
@@ -269,16 +221,16 @@ __global__ __launch_bounds__(256) void pathway16_mfma_kernel(const float* __rest
   }
   __syncthreads();
   // 3) 3x3 conv on MFMA: wave wv owns tile rows 4wv .. 4wv+3
-  floatx4_p acc[4];
+  floatx4_t acc[4];
 #pragma unroll
-  for (int rr = 0; rr < 4; ++rr) acc[rr] = floatx4_p{0.f, 0.f, 0.f, 0.f};
+  for (int rr = 0; rr < 4; ++rr) acc[rr] = floatx4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
     const int kh = t / 3, kw = t % 3;
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
       const int vox = (4 * wv + rr + kh) * kHalo + col + kw;
-      const float4 b = *reinterpret_cast<const float4*>(inb + vox * 16 + 4 * (kgrp ^ ((vox >> 1) & 3)));
+      const float4 b = *reinterpret_cast<const float4*>(inb + halo16_index(vox, kgrp));  // channels 4j + kgrp, j < 4
       acc[rr] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t][0], b.x, acc[rr], 0, 0, 0);
       acc[rr] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t][1], b.y, acc[rr], 0, 0, 0);
       acc[rr] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t][2], b.z, acc[rr], 0, 0, 0);

@@ -4,28 +4,10 @@
 //   tmvs_upsample2_add_nhwc      u = F.interpolate(r, 2x, bilinear, align_corners=False) + lateral
 //   tmvs_upsample2_backward_nhwc dr = the adjoint of that interpolation (a gather over the <= 4x4
 //                                fine pixels whose bilinear sample reads each coarse pixel)
-// Source index math: area_pixel_compute_source_index (align_corners=False): src = 0.5*(dst+0.5)-0.5,
-// clamped at 0; i0 = floor(src), i1 = i0 + (i0 < in-1), l1 = src - i0 (upsample_bilinear2d).
+// Source index math: lin_axis_x2 (common.h), torch's align_corners=False axis for a doubled size.
 #include "common.h"
 
 namespace tmvs {
-
-struct Lin1 {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ Lin1 lin_x2(int dst, int in_size) {
-  float src = 0.5f * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  Lin1 a;
-  a.i0 = (int)src;  // src >= 0: truncation == floor
-  a.i0 = a.i0 < in_size - 1 ? a.i0 : in_size - 1;
-  a.i1 = a.i0 + (a.i0 < in_size - 1 ? 1 : 0);
-  a.l1 = src - (float)a.i0;
-  a.l0 = 1.f - a.l1;
-  return a;
-}
 
 // u[n][y][x][c] = (h0 * (w0 * r[y0][x0] + w1 * r[y0][x1]) + h1 * (w0 * r[y1][x0] + w1 * r[y1][x1])) + lateral[n][c][y][x]
 template <int C>
@@ -37,7 +19,7 @@ __global__ __launch_bounds__(256) void upsample2_add_kernel(const float* __restr
   const int x = (int)(i % W);
   const int y = (int)((i / W) % H);
   const int n = (int)(i / ((long)W * H));
-  const Lin1 ay = lin_x2(y, h), ax = lin_x2(x, w);
+  const LinAxis ay = lin_axis_x2(y, h), ax = lin_axis_x2(x, w);
   const float* rb = r + (size_t)n * h * w * C;
   const float* p00 = rb + ((size_t)ay.i0 * w + ax.i0) * C;
   const float* p01 = rb + ((size_t)ay.i0 * w + ax.i1) * C;
@@ -67,12 +49,12 @@ __global__ __launch_bounds__(256) void upsample2_backward_kernel(const float* __
   for (int c = 0; c < C; ++c) acc[c] = 0.f;
   for (int y = 2 * i - 1; y <= 2 * i + 2; ++y) {
     if (y < 0 || y >= H) continue;
-    const Lin1 ay = lin_x2(y, h);
+    const LinAxis ay = lin_axis_x2(y, h);
     const float wy = (ay.i0 == i ? ay.l0 : 0.f) + (ay.i1 == i ? ay.l1 : 0.f);
     if (wy == 0.f) continue;
     for (int x = 2 * j - 1; x <= 2 * j + 2; ++x) {
       if (x < 0 || x >= W) continue;
-      const Lin1 ax = lin_x2(x, w);
+      const LinAxis ax = lin_axis_x2(x, w);
       const float wx = (ax.i0 == j ? ax.l0 : 0.f) + (ax.i1 == j ? ax.l1 : 0.f);
       if (wx == 0.f) continue;
       const float ww = wy * wx;

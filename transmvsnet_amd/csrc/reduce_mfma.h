@@ -13,7 +13,6 @@ namespace tmvs {
 // chunk's rows and are added in wave order at the end. fp32 within a chunk, fp64 across chunks.
 // load_a(v, q) / load_b(v, q): float4 q of row v (zeros where a gathered tap is outside); out: the
 // block's A x BC partial, fp64. The next chunk's rows are loaded into registers while this chunk's MFMAs run.
-typedef float floatx4_t __attribute__((ext_vector_type(4)));
 // BROW: thread t stages B quads 2(t&3), 2(t&3)+1 of row t>>2 (BC = 32) with one loader call
 // load_b(v, q0, float4 (&)[2]) instead of quad t&7 of rows t>>3 and t>>3 + 32: a gathered B row whose
 // loader derives per-row state (the DCN sample geometry) derives it once for both quads. Same LDS
