@@ -61,11 +61,13 @@ def project(cam, X):
     return t[..., 0] / t[..., 2], t[..., 1] / t[..., 2], t[..., 2]
 
 
-def fusibile_ref(rgbd, cams, ref, consistent_threshold=3, depth_threshold=0.25):
+def fusibile_ref(rgbd, cams, ref, consistent_threshold=3, depth_threshold=0.25, return_sums=False):
     """The fusibile kernel for one reference camera (fusibile.cu:89-173).
 
     rgbd [V, H, W, 4] float32 (B, G, R, depth); cams: list of dicts (P [3,4], RK_inv [3,3], C4 [3],
-    fx). Returns (written [H, W] bool, coord [H, W, 3], texture [H, W, 3]) for the written pixels."""
+    fx). Returns (written [H, W] bool, coord [H, W, 3], texture [H, W, 3]) for the written pixels;
+    with return_sums also (count [H, W] int, sum_x [H, W, 3], sum_t [H, W, 3]), the number of agreeing
+    views and the sums before the division by count + 1."""
     v, h, w, _ = rgbd.shape
     ys, xs = np.mgrid[0:h, 0:w]
     ys = ys.astype(np.float64)
@@ -100,6 +102,8 @@ def fusibile_ref(rgbd, cams, ref, consistent_threshold=3, depth_threshold=0.25):
         count += act
     written = alive & (count >= consistent_threshold)
     n1 = (count + 1.0)[..., None]
+    if return_sums:
+        return written, sum_x / n1, sum_t / n1, count, sum_x, sum_t
     return written, sum_x / n1, sum_t / n1
 
 

@@ -20,7 +20,9 @@ namespace tmvs {
 
 namespace fz {
 constexpr int CAM = 32;  // floats per packed camera: P[12], RK_inv[9], C4[3], fx, pad
-constexpr float kDepthFloor = 425.001f;
+// The reference writes `depth <= 425.001` with a DOUBLE literal, so the float depth is compared as a
+// double: float32(425.001) rounds up to 425.00100708 and is a live depth there.
+constexpr double kDepthFloor = 425.001;
 }  // namespace fz
 
 __device__ __forceinline__ float4 fz_load(const float4* __restrict__ img, int W, int x, int y) {
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(256) void fusibile_kernel(const float4* __restrict_
   if (x >= W || y >= H) return;
   const size_t HW = (size_t)H * W;
   float4 sum_t = rgbd[ref * HW + (size_t)y * W + x];
-  if (!(sum_t.w > fz::kDepthFloor)) return;  // fusibile.cu:116 (depth <= 425.001 -> return)
+  if (!((double)sum_t.w > fz::kDepthFloor)) return;  // fusibile.cu:116 (depth <= 425.001 -> return)
   const float* cr = cams + ref * fz::CAM;
   float X[3];
   fz_3dpoint(cr, (float)x, (float)y, sum_t.w, X);
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(256) void fusibile_kernel(const float4* __restrict_
     const float ptx = tx / tz, pty = ty / tz, depth = tz;
     if (!(ptx >= 0.f && ptx < (float)W && pty >= 0.f && pty < (float)H)) continue;  // also rejects NaN
     const float4 t = fz_tex_linear(rgbd + i * HW, H, W, ptx + 0.5f, pty + 0.5f);
-    if (!(t.w > fz::kDepthFloor)) continue;
+    if (!((double)t.w > fz::kDepthFloor)) continue;  // fusibile.cu:141
     const float bx = cr[21] - ci[21], by = cr[22] - ci[22], bz = cr[23] - ci[23];
     const float base = sqrtf(fmaf(bz, bz, fmaf(by, by, bx * bx)));
     const float ddisp = (f * base) / depth, tdisp = (f * base) / t.w;
