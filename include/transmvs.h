@@ -229,7 +229,8 @@ int tmvs_fmt_pathway(const float* coarse, const float* lateral, long lat_view_st
 /* ------------------------------------------------------------------ native orchestration
  * Whole-FMT forward (models/FMT.py:147-177 inside FMT_with_pathway :212-226): embedding + PE,
  * the reference view's 4 self layers (the K/V of each output is reduced once for the matching
- * cross layer), then views 1..nv-1 through all 8 layers, batched.
+ * cross layer), then views 1..nv-1 through all 8 layers, batched: each self layer 2j and the
+ * cross layer 2j+1 after it as one launch per 16-token tile (bitwise two tmvs_fmt_apply launches).
  *   stage1 [nv][32][H][W] (NCHW, per-view stride view_stride floats), pe [32][pe_h][pe_w],
  *   enc_w  HOST array of 8 DEVICE pointers (packed EncoderLayer weights, layer order 0..7)
  *   tokens [nv][H*W][32] out (NHWC stage-1 features after the FMT).                         */
@@ -239,7 +240,7 @@ int tmvs_fmt_forward(const float* stage1, long view_stride, const float* pe, int
                      void* stream);
 /* tmvs_fmt_forward with the reference view's chain -- its self layers 0,2,4,6 and the K/V of their outputs
  * for the cross layers (FMT.py:155-158,173-174) -- on side_stream, concurrent with the source views' 8
- * layers on stream. Bitwise the tokens of tmvs_fmt_forward. side_stream forks from stream after the
+ * layers (4 self + cross pair launches) on stream. Bitwise the tokens of tmvs_fmt_forward. side_stream forks from stream after the
  * embedding and is joined back into stream before the call returns (one fork level: graph-capturable).
  * side_stream NULL (or == stream, or nv < 2) runs tmvs_fmt_forward. */
 size_t tmvs_fmt_forward_split_workspace(int nv, int l_tokens);

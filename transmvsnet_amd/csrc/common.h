@@ -20,6 +20,13 @@
 
 namespace tmvs {
 
+// fmt.hip, for pipeline.hip (no C-ABI entry): two encoder layers in one launch on x [nv][l_tokens][32], in
+// place: layer enc_w0 with each view's own K/V summary kv0 [nv][TMVS_KV_NFLOATS], then layer enc_w1 with
+// the one summary kv1 for every view. Bitwise tmvs_fmt_apply(kv0, stride TMVS_KV_NFLOATS) followed by
+// tmvs_fmt_apply(kv1, stride 0).
+int fmt_apply_pair(float* x, int nv, int l_tokens, const float* kv0, const float* enc_w0, const float* kv1,
+                   const float* enc_w1, void* stream);
+
 __device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
 
 typedef float floatx4_t __attribute__((ext_vector_type(4)));  // an MFMA accumulator / one 16-byte buffer load

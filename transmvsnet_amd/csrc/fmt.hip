@@ -11,6 +11,16 @@
 //                     msg = (Q·KV) Z, x = LN1(x + Wo msg + bo), x = LN2(x + W2 relu(W1 x + b1) + b2)
 // Cross layers read the reference view's (KV, Ksum) for every source view (kv stride 0):
 // the reference recomputes the identical values per view (FMT.py:170-176).
+//   fmt_pair        : on the source views, self layer 2j and cross layer 2j+1 in one launch
+//                     (fmt_apply_pair, for pipeline.hip). Both are per-token maps, and the cross layer's
+//                     K/V comes from the reference view, so nothing is reduced over the source tokens
+//                     between them: the tile stays in registers from one layer to the next (one token
+//                     load and one store per pair) and the tokens are bitwise those of two fmt_apply
+//                     launches -- the per-layer tile body apply_layer is the one copy both kernels run.
+//                     Two layers' fragments and vectors are 52.7 KB of LDS. 4-wave blocks would fit 3
+//                     times per CU, 3 waves/SIMD, and the one-round tiling of the C2 launch (15,552
+//                     tiles) would quantise to 6 tiles per wave; 8-wave blocks fit twice (4 waves/SIMD,
+//                     as the one-layer apply: 120 VGPRs) and stage the weights once per 8 waves.
 //
 // The token-wise linears are dense 32x32 / 32x64 / 64x32 GEMMs over tiles of 16 tokens on the
 // exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32: D = A.B + C as an fp32 FMA chain, the VALU
@@ -72,21 +82,29 @@ __global__ __launch_bounds__(256) void fmt_embed_kernel(const float* __restrict_
   }
 }
 
-__device__ __forceinline__ int kfeat(int s, int g) { return 16 * (s >> 2) + 4 * g + (s & 3); }
-
 // A fragments of a [OUT][IN] linear (TRANS: the packed matrix is stored [IN][OUT]), staged in LDS in
 // read order [mb][s/4][lane][4] with element (mb, s, l) = W[16mb + (l&15)][kfeat(s, l>>4)]: one
 // ds_read_b128 per lane serves 4 consecutive k-steps of an MFMA chain, and the 64 lanes read 1 KiB
 // contiguous (conflict-free).
+// The copy walks the packed matrix in memory order, four consecutive floats per thread (coalesced; one
+// 16-byte load where W is 16-byte aligned, as every TMVS_ENC_* offset of an aligned block is), and scatters
+// into the fragment: feature i sits at (s4, g, j) = (i >> 4, (i >> 2) & 3, i & 3), the inverse of kfeat
+// (the header comment's k-step order).
+// Four consecutive inputs of one output are one 16-byte fragment entry; with TRANS the four are consecutive
+// outputs, the same j of four neighbouring lanes.
 template <int OUT, int IN, bool TRANS>
 __device__ __forceinline__ void stage_afrag(const float* __restrict__ W, float* __restrict__ lds) {
   constexpr int N = OUT * IN;  // = (OUT/16) * (IN/16) * 64 lanes * 4
-  for (int idx = threadIdx.x; idx < N; idx += blockDim.x) {
-    const int j = idx & 3, l = (idx >> 2) & 63, rest = idx >> 8;
-    const int s4 = rest % (IN / 16), mb = rest / (IN / 16);
-    const int s = 4 * s4 + j;
-    const int o = 16 * mb + (l & 15), i = kfeat(s, l >> 4);
-    lds[idx] = TRANS ? W[i * OUT + o] : W[o * IN + i];
+  const bool aligned = (reinterpret_cast<size_t>(W) & 15) == 0;  // block-uniform
+  for (int e = 4 * threadIdx.x; e < N; e += 4 * blockDim.x) {
+    const float4 t = aligned ? ld4(W + e) : make_float4(W[e], W[e + 1], W[e + 2], W[e + 3]);
+    const int o = TRANS ? e % OUT : e / IN, i = TRANS ? e / OUT : e % IN;  // of t.x
+    const int at = (((o >> 4) * (IN / 16) + (i >> 4)) * 64 + 16 * ((i >> 2) & 3) + (o & 15)) * 4 + (i & 3);
+    if (TRANS) {
+      lds[at] = t.x, lds[at + 4] = t.y, lds[at + 8] = t.z, lds[at + 12] = t.w;
+    } else {
+      *reinterpret_cast<float4*>(lds + at) = t;
+    }
   }
 }
 
@@ -113,13 +131,15 @@ __device__ __forceinline__ void mfma_linear_lds(const float* __restrict__ fl, co
   }
 }
 
-// What the two tile-walking kernels (fmt_kv_partial_kernel, fmt_apply_kernel) share: 4 waves per
-// block, wave wv of block b walks tpw tiles of 16 tokens from tile (4b + wv) tpw.
+// What the tile-walking kernels (fmt_kv_partial_kernel, fmt_apply_kernel, fmt_pair_kernel) share: WPB
+// waves per block (4; the pair kernel 8), wave wv of block b walks tpw tiles of 16 tokens from tile
+// (WPB b + wv) tpw.
 //
 // the wave index, wave-uniform (readfirstlane): the tile loop is then scalar control flow, not a divergent
 // loop whose per-lane exits make the compiler wait vmcnt(0) (stores included) at its head
 __device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
-__device__ __forceinline__ int first_tile(int wv, int tpw) { return (blockIdx.x * 4 + wv) * tpw; }
+template <int WPB = 4>
+__device__ __forceinline__ int first_tile(int wv, int tpw) { return (blockIdx.x * WPB + wv) * tpw; }
 // an opaque 0 to offset LDS pointers by: the fragment reads stay in the loop (not hoisted back into VGPRs).
 // An SGPR: a VGPR here could alias a pending load (vmcnt wait)
 __device__ __forceinline__ int opaque_zero() {
@@ -305,100 +325,125 @@ __global__ __launch_bounds__(1024) void fmt_kv_combine_kernel(const float* __res
   }
 }
 
-// The rest of EncoderLayer.forward for tiles of 16 query tokens, entirely in registers.
-// (amdgpu_waves_per_eu(5) fits it in 94 VGPRs without AGPRs, 5 waves/SIMD instead of 4: the 8 applies
-// measured 456.6 vs 448.1 us per step, 6 waves (80 VGPRs + scratch) 472.0 -- profiles/r11n: not kept.
-// Two tiles per call of the tile lambda, their MFMA chains interleaved, was an option nobody selected.)
-__global__ __launch_bounds__(256) void fmt_apply_kernel(float* __restrict__ x, int L, const float* __restrict__ kvg,
-                                                        long kv_stride, const float* __restrict__ w, int tpw) {
-  __shared__ __attribute__((aligned(16))) float kvs[kKV];
-  // the per-feature vectors, read from LDS in the tile loop: a global load there is a full memory
-  // latency, and its vmcnt(0) wait also drains the next tile's token prefetch
-  // [0, 32) BQ  [32, 64) BO  [64, 128) B1  [128, 160) B2  [160, 288) LN1G LN1B LN2G LN2B
-  constexpr int kVB2 = 128, kVLN = 160;
-  __shared__ __attribute__((aligned(16))) float vec[288];
-  const int v = blockIdx.y;
-  const int lane = threadIdx.x & 63, wv = wave_index();
-  const int g = lane >> 4;
-  if (threadIdx.x < kKV) kvs[threadIdx.x] = kvg[(size_t)v * kv_stride + threadIdx.x];
-  for (int i = threadIdx.x; i < 288; i += blockDim.x)
+// One encoder layer's share of LDS in the applies: the view's K/V summary, the per-feature vectors (read
+// from LDS in the tile loop: a global load there is a full memory latency, and its vmcnt(0) wait also
+// drains the next tile's token prefetch) and the Wq, Wo, W1, W2 fragments.
+// vec: [0, 32) BQ  [32, 64) BO  [64, 128) B1  [128, 160) B2  [160, 288) LN1G LN1B LN2G LN2B
+constexpr int kVB2 = 128, kVLN = 160, kVec = 288;
+constexpr int kApplyFrag = 32 * 32 * 2 + 64 * 32 * 2;
+__device__ __forceinline__ void stage_layer(const float* __restrict__ w, const float* __restrict__ kv,
+                                            float* __restrict__ kvs, float* __restrict__ vec,
+                                            float* __restrict__ frag) {
+  if (threadIdx.x < kKV) kvs[threadIdx.x] = kv[threadIdx.x];
+  for (int i = threadIdx.x; i < kVec; i += blockDim.x)
     vec[i] = i < 32 ? w[TMVS_ENC_BQ + i] : i < 64 ? w[TMVS_ENC_BO + i - 32] : i < 128 ? w[TMVS_ENC_B1 + i - 64]
                                                                                       : w[TMVS_ENC_B2 + i - kVB2];
-  __shared__ __attribute__((aligned(16))) float frag[32 * 32 * 2 + 64 * 32 * 2];  // Wq, Wo, W1, W2 fragments
   stage_afrag<32, 32, false>(w + TMVS_ENC_WQ, frag);
   stage_afrag<32, 32, false>(w + TMVS_ENC_WO, frag + 1024);
   stage_afrag<64, 32, false>(w + TMVS_ENC_W1, frag + 2048);
   stage_afrag<32, 64, true>(w + TMVS_ENC_W2T, frag + 4096);
+}
+
+// The rest of EncoderLayer.forward for one tile of 16 query tokens xs, entirely in registers: the one
+// copy of the per-token arithmetic, shared by fmt_apply_kernel and fmt_pair_kernel (fr, vb, kvs: the
+// layer's LDS as staged by stage_layer).
+__device__ __forceinline__ void apply_layer(floatx4_t (&xs)[2], const float* fr, const float* vb, const float* kvs,
+                                            int lane) {
+  const int g = lane >> 4;
+  floatx4_t q[2], msg[2];
+  mfma_linear_lds<32, 32>(fr, xs, q, lane);
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb) {
+    const int h = 4 * mb + g;
+    // head h's K/V summary, bias and Ksum as 16-byte LDS reads issued together
+    float bq[4], ksum[4], kvm[4][4];
+    ld4(vb + 4 * h, bq);
+    ld4(kvs + ksum_at(h, 0), ksum);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) ld4(kvs + kv_at(h, m, 0), kvm[m]);
+    float qe[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) qe[d] = elu1(q[mb][d] + bq[d]);
+    float den = 0.f;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) den = fmaf(qe[d], ksum[d], den);
+    const float z = 1.f / (den + kAttnEps);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      float num = 0.f;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) num = fmaf(qe[d], kvm[m][d], num);
+      msg[mb][m] = num * z;
+    }
+  }
+  floatx4_t a[2];
+  mfma_linear_lds<32, 32>(fr + 1024, msg, a, lane);
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb) {
+    float bo[4];
+    ld4(vb + 32 + 16 * mb + 4 * g, bo);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) xs[mb][r] = xs[mb][r] + (a[mb][r] + bo[r]);
+  }
+  layer_norm_frag(xs, vb + kVLN, vb + kVLN + kD, lane);
+  floatx4_t hdn[4], ff[2];
+  mfma_linear_lds<64, 32>(fr + 2048, xs, hdn, lane);
+#pragma unroll
+  for (int mb = 0; mb < 4; ++mb) {
+    float b1[4];
+    ld4(vb + 64 + 16 * mb + 4 * g, b1);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) hdn[mb][r] = relu(hdn[mb][r] + b1[r]);
+  }
+  mfma_linear_lds<32, 64>(fr + 4096, hdn, ff, lane);
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb) {
+    float b2[4];
+    ld4(vb + kVB2 + 16 * mb + 4 * g, b2);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) xs[mb][r] = xs[mb][r] + (ff[mb][r] + b2[r]);
+  }
+  layer_norm_frag(xs, vb + kVLN + 2 * kD, vb + kVLN + 3 * kD, lane);
+}
+
+// NL encoder layers in a row on each 16-token tile of view blockIdx.y, WPB waves per block: the tile is
+// loaded once, stays in registers between the layers and is stored once. Layer i has weights w[i] and
+// reads view v's K/V summary at kv[i] + v kv_stride[i] (stride 0: one summary for every view).
+struct LayerArgs {
+  const float* w;
+  const float* kv;
+  long kv_stride;
+};
+template <int NL, int WPB>
+__device__ __forceinline__ void apply_tiles(float* __restrict__ x, int L, const LayerArgs (&layer)[NL], int tpw) {
+  __shared__ __attribute__((aligned(16))) float kvs[NL][kKV];
+  __shared__ __attribute__((aligned(16))) float vec[NL][kVec];
+  __shared__ __attribute__((aligned(16))) float frag[NL][kApplyFrag];
+  const int v = blockIdx.y;
+  const int lane = threadIdx.x & 63, wv = wave_index();
+  const int g = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < NL; ++i)
+    stage_layer(layer[i].w, layer[i].kv + (size_t)v * layer[i].kv_stride, kvs[i], vec[i], frag[i]);
   __syncthreads();
   float* xv = x + (size_t)v * L * kD;
-  const int tile0 = first_tile(wv, tpw);
+  const int tile0 = first_tile<WPB>(wv, tpw);
   // two token buffers used alternately (the loop unrolled by two, so they swap by name: a
   // loop-carried copy made the compiler wait vmcnt(0) -- this tile's stores included -- at the latch)
   floatx4_t xa[2], xb[2];
   load_token_frag(row(xv, tile0 * 16 + (lane & 15), L), xa, lane);
   auto tile = [&](int it, floatx4_t (&cur)[2], floatx4_t (&nxt)[2]) {
     const int salt = opaque_zero();
-    const float* fr = frag + salt;
-    const float* vb = vec + salt;
     const int t = (tile0 + it) * 16 + (lane & 15);
     const bool ok = t < L;
     float* out = row(xv, t, L);
     floatx4_t xs[2] = {cur[0], cur[1]};
     load_token_frag(row(xv, t + 16, L), nxt, lane);
-    floatx4_t q[2], msg[2];
-    mfma_linear_lds<32, 32>(fr, xs, q, lane);
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-      const int h = 4 * mb + g;
-      // head h's K/V summary, bias and Ksum as 16-byte LDS reads issued together
-      float bq[4], ksum[4], kvm[4][4];
-      ld4(vb + 4 * h, bq);
-      ld4(kvs + ksum_at(h, 0), ksum);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) ld4(kvs + kv_at(h, m, 0), kvm[m]);
-      float qe[4];
-#pragma unroll
-      for (int d = 0; d < 4; ++d) qe[d] = elu1(q[mb][d] + bq[d]);
-      float den = 0.f;
-#pragma unroll
-      for (int d = 0; d < 4; ++d) den = fmaf(qe[d], ksum[d], den);
-      const float z = 1.f / (den + kAttnEps);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        float num = 0.f;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) num = fmaf(qe[d], kvm[m][d], num);
-        msg[mb][m] = num * z;
-      }
-    }
-    floatx4_t a[2];
-    mfma_linear_lds<32, 32>(fr + 1024, msg, a, lane);
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-      float bo[4];
-      ld4(vb + 32 + 16 * mb + 4 * g, bo);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) xs[mb][r] = xs[mb][r] + (a[mb][r] + bo[r]);
-    }
-    layer_norm_frag(xs, vb + kVLN, vb + kVLN + kD, lane);
-    floatx4_t hdn[4], ff[2];
-    mfma_linear_lds<64, 32>(fr + 2048, xs, hdn, lane);
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb) {
-      float b1[4];
-      ld4(vb + 64 + 16 * mb + 4 * g, b1);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) hdn[mb][r] = relu(hdn[mb][r] + b1[r]);
-    }
-    mfma_linear_lds<32, 64>(fr + 4096, hdn, ff, lane);
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-      float b2[4];
-      ld4(vb + kVB2 + 16 * mb + 4 * g, b2);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) xs[mb][r] = xs[mb][r] + (ff[mb][r] + b2[r]);
-    }
-    layer_norm_frag(xs, vb + kVLN + 2 * kD, vb + kVLN + 3 * kD, lane);
+    // (written out, not a loop over NL: as an unrolled loop of one trip the one-layer kernel came out at 240
+    // VGPRs, 2 waves/SIMD, instead of 101 + 24 AGPRs)
+    static_assert(NL == 1 || NL == 2, "layers per launch");
+    apply_layer(xs, frag[0] + salt, vec[0] + salt, kvs[0], lane);
+    if constexpr (NL == 2) apply_layer(xs, frag[1] + salt, vec[1] + salt, kvs[1], lane);
     if (ok) {
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb)
@@ -414,18 +459,50 @@ __global__ __launch_bounds__(256) void fmt_apply_kernel(float* __restrict__ x, i
   }
 }
 
-// Resident 4-wave blocks of `kernel` on the whole GPU (its occupancy at 256 threads: VGPRs, LDS)
+// One encoder layer on every view of the launch.
+// (amdgpu_waves_per_eu(5) fits it in 94 VGPRs without AGPRs, 5 waves/SIMD instead of 4: the 8 applies
+// measured 456.6 vs 448.1 us per step, 6 waves (80 VGPRs + scratch) 472.0 -- profiles/r11n: not kept.
+// Two tiles per call of the tile lambda, their MFMA chains interleaved, was an option nobody selected.)
+__global__ __launch_bounds__(256) void fmt_apply_kernel(float* __restrict__ x, int L, const float* __restrict__ kvg,
+                                                        long kv_stride, const float* __restrict__ w, int tpw) {
+  const LayerArgs layer[1] = {{w, kvg, kv_stride}};
+  apply_tiles<1, 4>(x, L, layer, tpw);
+}
+
+// Self layer 2j with each source view's own K/V (w0, kv0), then cross layer 2j+1 with the reference
+// view's (w1, kv1, stride 0), on the source views: both are per-token maps and no reduction over the source
+// tokens sits between them, so the tokens are bitwise those of two fmt_apply_kernel launches without the
+// round trip through memory in between. Blocks of 8 waves: two layers' fragments are 52 KB, which 4-wave
+// blocks would fit 3 times per CU (3 waves/SIMD); two 8-wave blocks keep the apply's 4 waves/SIMD and
+// stage the weights half as often.
+constexpr int kPairWaves = 8;
+__global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu(4))) void fmt_pair_kernel(float* __restrict__ x, int L,
+                                                                   const float* __restrict__ kv0, long kv0_stride,
+                                                                   const float* __restrict__ w0,
+                                                                   const float* __restrict__ kv1, long kv1_stride,
+                                                                   const float* __restrict__ w1, int tpw) {
+  const LayerArgs layer[2] = {{w0, kv0, kv0_stride}, {w1, kv1, kv1_stride}};
+  apply_tiles<2, kPairWaves>(x, L, layer, tpw);
+}
+
+// Resident blocks of `kernel` on the whole GPU (its occupancy at `threads` per block: VGPRs, LDS)
 template <typename K>
-static long block_slots(K kernel) {
+static long block_slots(K kernel, int threads = 256) {
   int dev = 0, cus = 0, per = 0;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, 256, 0) != hipSuccess || per <= 0) per = 4;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, threads, 0) != hipSuccess || per <= 0)
+    per = 1024 / threads;
   return (long)(cus > 0 ? cus : 256) * per;
 }
 static int wave_slots_apply() {
   static long slots = 0;
   if (!slots) slots = 4 * block_slots(fmt_apply_kernel);
+  return (int)slots;
+}
+static int wave_slots_pair() {
+  static long slots = 0;
+  if (!slots) slots = kPairWaves * block_slots(fmt_pair_kernel, 64 * kPairWaves);
   return (int)slots;
 }
 
@@ -448,11 +525,11 @@ static int kv_nblk(int nv, int S) {
 // 92 VGPRs since the bias vectors moved to LDS): with a fixed 4 tiles per wave the C2 grid (5 x 3888
 // tiles = 4.75 waves per SIMD at 4/SIMD) ran as a full round plus a 3/4-empty second one (2.4
 // waves/SIMD on average, r05f).
-static int apply_tiles_per_wave(int nv, int L) {
+static int apply_tiles_per_wave(int nv, int L, int wave_slots) {
   const long tiles = (long)nv * ((L + 15) / 16);
-  return (int)std::max<long>(1, (tiles + wave_slots_apply() - 1) / wave_slots_apply());
+  return (int)std::max<long>(1, (tiles + wave_slots - 1) / wave_slots);
 }
-static int apply_nblk(int L, int tpw) { return (L + 16 * 4 * tpw - 1) / (16 * 4 * tpw); }
+static int apply_nblk(int L, int tpw, int wpb) { return (L + 16 * wpb * tpw - 1) / (16 * wpb * tpw); }
 
 }  // namespace tmvs
 
@@ -501,8 +578,8 @@ extern "C" int tmvs_fmt_kv(const float* source, int nv, int s_tokens, const floa
 extern "C" int tmvs_fmt_apply_tiled(float* x, int nv, int l_tokens, const float* kv, long kv_view_stride,
                                     const float* enc_w, int tiles_per_wave, void* stream) {
   if (!x || !kv || !enc_w || nv <= 0 || l_tokens <= 0 || kv_view_stride < 0) return TMVS_ERR_ARG;
-  const int tpw = tiles_per_wave > 0 ? tiles_per_wave : apply_tiles_per_wave(nv, l_tokens);
-  hipLaunchKernelGGL(fmt_apply_kernel, dim3(apply_nblk(l_tokens, tpw), nv), dim3(256), 0, (hipStream_t)stream, x,
+  const int tpw = tiles_per_wave > 0 ? tiles_per_wave : apply_tiles_per_wave(nv, l_tokens, wave_slots_apply());
+  hipLaunchKernelGGL(fmt_apply_kernel, dim3(apply_nblk(l_tokens, tpw, 4), nv), dim3(256), 0, (hipStream_t)stream, x,
                      l_tokens, kv, kv_view_stride, enc_w, tpw);
   TMVS_CHECK_LAUNCH();
   return TMVS_OK;
@@ -511,4 +588,17 @@ extern "C" int tmvs_fmt_apply_tiled(float* x, int nv, int l_tokens, const float*
 extern "C" int tmvs_fmt_apply(float* x, int nv, int l_tokens, const float* kv, long kv_view_stride,
                               const float* enc_w, void* stream) {
   return tmvs_fmt_apply_tiled(x, nv, l_tokens, kv, kv_view_stride, enc_w, 0, stream);
+}
+
+// Layers (w0, kv0: per view) then (w1, kv1: one summary for every view) on each token of x [nv][L][32] in one
+// launch (fmt_pair_kernel): bitwise tmvs_fmt_apply with kv0, then tmvs_fmt_apply with kv1 and stride 0.
+// Library-internal (common.h): reached through tmvs_fmt_forward and tmvs_fmt_forward_split.
+int tmvs::fmt_apply_pair(float* x, int nv, int l_tokens, const float* kv0, const float* enc_w0, const float* kv1,
+                         const float* enc_w1, void* stream) {
+  if (!x || !kv0 || !enc_w0 || !kv1 || !enc_w1 || nv <= 0 || l_tokens <= 0) return TMVS_ERR_ARG;
+  const int tpw = apply_tiles_per_wave(nv, l_tokens, wave_slots_pair());
+  hipLaunchKernelGGL(fmt_pair_kernel, dim3(apply_nblk(l_tokens, tpw, kPairWaves), nv), dim3(64 * kPairWaves), 0,
+                     (hipStream_t)stream, x, l_tokens, kv0, (long)kKV, enc_w0, kv1, 0L, enc_w1, tpw);
+  TMVS_CHECK_LAUNCH();
+  return TMVS_OK;
 }

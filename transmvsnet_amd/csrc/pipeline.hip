@@ -31,16 +31,19 @@ extern "C" int tmvs_fmt_forward(const float* stage1, long view_stride, const flo
   int rc;
   if ((rc = tmvs_fmt_embed(stage1, view_stride, pe, pe_h, pe_w, nv, 32, height, width, tokens, stream))) return rc;
   // Self layers 0,2,4,6 carry the same weights for the reference view (FMT.py:155-158) and the
-  // source views (:171-172): each runs on all nv views in one launch (per-view K/V). The
-  // reference output of self layer 2j is ref_feature_list[j], the K/V source of cross layer 2j+1.
+  // source views (:171-172): their K/V summaries come from one launch over all nv views. The
+  // reference output of self layer 2j is ref_feature_list[j], the K/V source of cross layer 2j+1;
+  // the source views then run self layer 2j and cross layer 2j+1 as one launch (fmt_apply_pair).
   float* src = tokens + (size_t)L * 32;
   for (int j = 0; j < 4; ++j) {
     const int i = 2 * j;
     if ((rc = tmvs_fmt_kv(tokens, nv, L, enc_w[i], kv_ws, slab, kv_self, stream))) return rc;
-    if ((rc = tmvs_fmt_apply(tokens, nv, L, kv_self, TMVS_KV_NFLOATS, enc_w[i], stream))) return rc;
+    if ((rc = tmvs_fmt_apply(tokens, 1, L, kv_self, TMVS_KV_NFLOATS, enc_w[i], stream))) return rc;
     if (nv == 1) continue;
     if ((rc = tmvs_fmt_kv(tokens, 1, L, enc_w[i + 1], kv_ws, slab, kv_cross + j * TMVS_KV_NFLOATS, stream))) return rc;
-    if ((rc = tmvs_fmt_apply(src, nv - 1, L, kv_cross + j * TMVS_KV_NFLOATS, 0, enc_w[i + 1], stream))) return rc;
+    if ((rc = tmvs::fmt_apply_pair(src, nv - 1, L, kv_self + TMVS_KV_NFLOATS, enc_w[i], kv_cross + j * TMVS_KV_NFLOATS,
+                                   enc_w[i + 1], stream)))
+      return rc;
   }
   return TMVS_OK;
 }
@@ -92,7 +95,7 @@ SplitEvents* split_events() {
 
 // models/FMT.py:147-177 as two dependency chains: the reference view's self layers 0,2,4,6 (FMT.py:155-158)
 // and the K/V reductions of its outputs for the cross layers (:173-174) on side_stream; the source views'
-// 8 layers (:168-175) on stream, each cross layer waiting for its K/V. Self-layer K/V keep the nv-view
+// 8 layers (:168-175) on stream as 4 self + cross pairs, each pair waiting for its cross layer's K/V. Self-layer K/V keep the nv-view
 // launch's partial grouping (tmvs_fmt_kv_grouped) and the applies are per token, so the tokens are bitwise
 // those of tmvs_fmt_forward. side_stream forks from stream after the embedding and joins before return.
 extern "C" int tmvs_fmt_forward_split(const float* stage1, long view_stride, const float* pe, int pe_h, int pe_w,
@@ -129,21 +132,21 @@ extern "C" int tmvs_fmt_forward_split(const float* stage1, long view_stride, con
     if ((r = tmvs_fmt_kv(tokens, 1, L, enc_w[i + 1], slab_side, sd, kv_cross + j * TMVS_KV_NFLOATS, ss))) return r;
     return hipEventRecord(e->ev[1 + j], ss) != hipSuccess ? TMVS_ERR_HIP : TMVS_OK;
   };
-  auto src_self = [&](int j) -> int {  // source views: self layer 2j
+  // source views: self layer 2j and cross layer 2j+1 as one launch, which waits for the reference's K/V. (At
+  // j = 0 that K/V arrives after the source views' own, so pair 0 starts late; with its self layer as a launch
+  // of its own in the meantime the FMT alone measured 518 us against 503, the step the same: DESIGN.md)
+  auto src_pair = [&](int j) -> int {
     const int i = 2 * j;
     int r;
     if ((r = tmvs_fmt_kv_grouped(src, nv - 1, nv, L, enc_w[i], slab_main, sm, kv_src, ms))) return r;
-    return tmvs_fmt_apply(src, nv - 1, L, kv_src, TMVS_KV_NFLOATS, enc_w[i], ms);
-  };
-  auto src_cross = [&](int j) -> int {  // source views: cross layer 2j+1 (waits for the reference's K/V)
     if (hipStreamWaitEvent(ms, e->ev[1 + j], 0) != hipSuccess) return TMVS_ERR_HIP;
-    return tmvs_fmt_apply(src, nv - 1, L, kv_cross + j * TMVS_KV_NFLOATS, 0, enc_w[2 * j + 1], ms);
+    return tmvs::fmt_apply_pair(src, nv - 1, L, kv_src, enc_w[i], kv_cross + j * TMVS_KV_NFLOATS, enc_w[i + 1], ms);
   };
   // the reference chain enqueued whole, then the source views'
   for (int j = 0; j < 4; ++j)
     if ((rc = ref_layer(j))) return rc;
   for (int j = 0; j < 4; ++j)
-    if ((rc = src_self(j)) || (rc = src_cross(j))) return rc;
+    if ((rc = src_pair(j))) return rc;
   if (hipEventRecord(e->ev[5], ss) != hipSuccess) return TMVS_ERR_HIP;
   if (hipStreamWaitEvent(ms, e->ev[5], 0) != hipSuccess) return TMVS_ERR_HIP;
   return TMVS_OK;

@@ -391,6 +391,9 @@ def fmt_pathway(coarse_nhwc, lateral_nchw, w_reduce, w_smooth, out=None):
     """smooth(up2(reduce(coarse)) + lateral) (FMT.py:221-228): coarse [nv,h,w,cc], lateral [nv,cf,2h,2w].
 
     out: optional contiguous [nv,2h,2w,cf] destination (e.g. a view slice of a larger batch)."""
+    for name, t in (("coarse", coarse_nhwc), ("lateral", lateral_nchw), ("w_reduce", w_reduce), ("w_smooth", w_smooth),
+                    ("out", out)):
+        _dev(t, name)
     nv, h, w, cc = coarse_nhwc.shape
     cf = lateral_nchw.shape[1]
     if out is None:
