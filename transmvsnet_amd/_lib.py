@@ -143,6 +143,14 @@ SYNC_SIGNATURES = {
     "tmvs_pw_sync_backward_apply": (I, [P, I, I, I, I, I, P, P, P, P, P, P, P, L, P, P, P, S, P, P, P]),
 }
 
+# name -> (restype, argtypes); every symbol include/transmvs_view_select.h declares (view selection for a COLMAP
+# sparse model: view_select.py)
+VS_SIGNATURES = {
+    "tmvs_vs_set_bits": (I, [P, P, L, I, L, P, P, P]),
+    "tmvs_vs_obs_depth": (I, [P, P, L, I, L, P, P, P, P, P, P]),
+    "tmvs_vs_pair_scores": (I, [P, I, L, P, P, D, D, D, P, P, P]),
+}
+
 ABI_VERSION = 11
 PW_NPARAMS = 201
 ENC_NPARAMS = 8544
@@ -158,6 +166,8 @@ DYNFUSE_MAX_SRC = 10
 DYNFUSE_PHOTO, DYNFUSE_GEO, DYNFUSE_FINAL = 1, 2, 4
 DTU_UNDECIDED, DTU_KEPT, DTU_REMOVED = 0, 1, 2
 GT_BLD, GT_DTU = 0, 1
+VS_MAX_BITS_BYTES = 1 << 30
+VS_MAX_BLOCKS = 2048
 
 
 class CostRegWeights(ctypes.Structure):
@@ -177,7 +187,7 @@ def load():
         raise RuntimeError(f"transmvsnet_amd HIP extension not built ({LIB_PATH} missing): "
                            "run `python -m transmvsnet_amd.build`")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (*SIGNATURES.items(), *SYNC_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *SYNC_SIGNATURES.items(), *VS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

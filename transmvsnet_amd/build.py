@@ -21,7 +21,7 @@ ARCH = os.environ.get("TMVS_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["host.hip", "glue.hip", "warp_corr.hip", "costreg.hip", "fmt.hip", "pathway.hip", "pipeline.hip", "featurenet.hip",
            "conv2d.hip", "fusion.hip", "dynamic_fusion.hip", "postprocess.hip", "loss.hip", "costreg_train.hip", "pw_train.hip", "pathway_train.hip",
-           "fmt_train.hip", "optim.hip", "featurenet_train.hip", "dtu_eval.hip", "train_data.hip", "sync_reduce.hip"]
+           "fmt_train.hip", "optim.hip", "featurenet_train.hip", "dtu_eval.hip", "train_data.hip", "sync_reduce.hip", "view_select.hip"]
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=off", "-fno-gpu-rdc",
           "-Wall", "-Wno-unused-function", "-I", os.path.join(ROOT, "include")]
 
@@ -36,7 +36,7 @@ def _newer(src_paths, dst):
 def _compile(src, force):
     s = os.path.join(CSRC, src)
     o = os.path.join(OBJ, src.replace(".hip", ".o"))
-    deps = [s] + [os.path.join(ROOT, "include", h) for h in ("transmvs.h", "transmvs_sync.h")] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
+    deps = [s] + [os.path.join(ROOT, "include", h) for h in ("transmvs.h", "transmvs_sync.h", "transmvs_view_select.h")] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     if not force and not _newer(deps, o):
         return o, None
     cmd = [HIPCC, *CFLAGS, "-c", s, "-o", o]

@@ -446,6 +446,9 @@ def make_parser():
     p.add_argument("--num_view", type=int, default=None, help="views per forward (default 5 for dtu, 11 for tnt)")
     p.add_argument("--photo_threshold", type=float, default=0.3, help="tnt: photo threshold for filter confidence")
     p.add_argument("--thres_view", type=int, default=3, help="tnt: threshold of num view")
+    p.add_argument("--image_size", type=int, nargs=2, default=None, metavar=("W", "H"),
+                   help="tnt: the (max_w, max_h) images are fitted into, for a scan outside data.TNT_IMAGE_SIZES "
+                        "(a folder written by transmvsnet_amd.colmap_scene)")
     p.add_argument("--save_outputs", action="store_true",
                    help="also write the per-view files the reference leaves on disk")
     return p
@@ -483,7 +486,7 @@ def main(argv=None):
         res = reconstruct_scan(model, args.testpath, scan, args.dataset, args.outdir, nviews=args.num_view,
                                max_h=args.max_h, max_w=args.max_w, photo_threshold=args.photo_threshold,
                                thres_view=args.thres_view, save_outputs=args.save_outputs, fixed_hw=fixed_hw,
-                               verbose=True)
+                               image_size=tuple(args.image_size) if args.image_size else None, verbose=True)
         fixed_hw = res["fixed_hw"]
 
 

@@ -263,3 +263,64 @@ def write_dtu_train_scan(root, scan="scan1", n_views=3, height=128, width=160, m
     with open(listfile, "w") as f:
         f.write(scan + "\n")
     return listfile
+
+
+# ------------------------------------------------------------------ COLMAP sparse models on disk
+def _rot_to_quat(R):
+    """The Hamilton quaternion (w, x, y, z), w >= 0, of a rotation matrix (Shepperd's branches)."""
+    R = np.asarray(R, np.float64)
+    tr = np.trace(R)
+    if tr > 0:
+        s = math.sqrt(tr + 1.0) * 2
+        q = [0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s]
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = math.sqrt(1.0 + R[i, i] - R[j, j] - R[k, k]) * 2
+        q = [0.0] * 4
+        q[0], q[1 + i], q[1 + j], q[1 + k] = (R[k, j] - R[j, k]) / s, 0.25 * s, (R[j, i] + R[i, j]) / s, (R[k, i] + R[i, k]) / s
+    q = np.array(q, np.float64)
+    q = q / np.linalg.norm(q)
+    return -q if q[0] < 0 else q
+
+
+def write_colmap_model(root, n_views=6, n_points=300, height=128, width=160, seed=1, binary=True, spread=220.0):
+    """A small COLMAP sparse model under `root` (cameras / images / points3D as .bin or .txt, colmap.write_raw):
+    synthetic_cameras' rig with full-size PINHOLE intrinsics, image ids 2 v + 1 named view_{v:03}.png, and
+    n_points random points round the rig's target (x, y within +-spread, z in 600..700; ids 10 + 3 p), each
+    observed by the views it projects into (0 <= u < width, 0 <= v < height, z > 0). Returns what it wrote: the
+    three dictionaries of colmap.read_raw under "cameras", "images", "points3D", and the arrays colmap.read_model
+    gives for them: "image_ids", "names", "K", "R", "t", "centres", "point_ids", "xyz", "obs"."""
+    from . import colmap
+    rng = np.random.default_rng([int(seed), 77])
+    cams = synthetic_cameras(n_views, height, width, seed=seed)["stage1"][0].numpy().astype(np.float64)
+    xyz = np.stack([rng.uniform(-spread, spread, n_points), rng.uniform(-spread, spread, n_points),
+                    rng.uniform(600.0, 700.0, n_points)], 1)
+    point_ids = 10 + 3 * np.arange(n_points)
+    cameras, images, tracks, obs = {}, {}, [[] for _ in range(n_points)], []
+    K_all, R_all, t_all = [], [], []
+    for v in range(n_views):
+        K = cams[v, 1, :3, :3].copy()
+        K[:2] *= 4.0
+        q = _rot_to_quat(cams[v, 0, :3, :3])
+        R, t = colmap.quat_to_rot(q), cams[v, 0, :3, 3].copy()
+        cameras[v + 1] = ("PINHOLE", width, height, np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]]))
+        pc = xyz @ R.T + t
+        uv = pc[:, :2] / pc[:, 2:3] * [K[0, 0], K[1, 1]] + [K[0, 2], K[1, 2]]
+        seen = np.nonzero((pc[:, 2] > 0) & (uv[:, 0] >= 0) & (uv[:, 0] < width) & (uv[:, 1] >= 0) & (uv[:, 1] < height))[0]
+        # one 2-D point without a 3-D point in front, as COLMAP's images carry
+        xy = np.concatenate([[[0.5, 0.5]], uv[seen]])
+        ids = np.concatenate([[-1], point_ids[seen]]).astype(np.int64)
+        for k, p in enumerate(seen):
+            tracks[p].append((2 * v + 1, k + 1))
+        images[2 * v + 1] = (q, t, v + 1, "view_{:03}.png".format(v), xy, ids)
+        obs.append(np.stack([np.full(seen.size, v), seen], 1))
+        K_all.append(K), R_all.append(R), t_all.append(t)
+    points3D = {int(point_ids[p]): (xyz[p], rng.integers(0, 256, 3).astype(np.uint8), float(rng.uniform(0.1, 1.0)),
+                                    np.array(tracks[p], np.int32).reshape(-1, 2)) for p in range(n_points)}
+    colmap.write_raw(root, cameras, images, points3D, binary)
+    R_all, t_all = np.stack(R_all), np.stack(t_all)
+    return {"cameras": cameras, "images": images, "points3D": points3D, "image_ids": 2 * np.arange(n_views) + 1,
+            "names": [images[2 * v + 1][3] for v in range(n_views)], "K": np.stack(K_all), "R": R_all, "t": t_all,
+            "centres": np.stack([-R.T @ t for R, t in zip(R_all, t_all)]), "point_ids": point_ids, "xyz": xyz,
+            "obs": np.concatenate(obs).astype(np.int32)}
